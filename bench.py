@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- (A, grad A) evaluations per second of the variational-annealing action
-on MI355X, against the HBM roofline, with the CPU oracle timed beside it.
+on MI355X, against the HBM roofline (with --full: the CPU oracle timed beside it).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c4|c2] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c4|c2] [--full [--no-cpu] [--no-extra]]
+                    [--dump-outputs DIR]
 
 A "step" is ONE complete batched evaluation -- the launch va_action_grad makes: the action
 A(X,p) (me + fe formed on the device by the last-arriving workgroup of each seed) and its full
 gradient for all B resident seeds.  Paths are resident in HBM before the timed region.
-The default run (1 GPU) also reports, in `extra`: the C4 shape, the end-to-end C3 ladder with
-the two L-BFGS vector kernels priced against the roofline, and the CPU oracle on all host cores.  N>1: one process per GPU (torch.distributed over RCCL), B seeds per
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else.
+With --full the run also times the CPU oracle (one core, all usable cores, the NumPy twin) and, for c3 on
+1 GPU, reports in `extra`: the C4 shape, the end-to-end C3 ladder with the two L-BFGS vector kernels priced
+against the roofline, the discretisation variants, the network action and the MNIST-shaped run.
+--dump-outputs DIR writes what the last timed step left for a caller (A, me, fe, gradient) as .npy files;
+the inputs are seeded, so two builds can be compared output for output.  N>1: one process per GPU (torch.distributed over RCCL), B seeds per
 GPU (weak scaling), no data-path collective; the job's one all_gather of the per-seed
 actions is issued after the K timed steps and timed separately (config.final_gather_ms).
 
@@ -54,6 +59,9 @@ F64_MFMA_PEAK_TFLOPS = 78.6    # MI355X FP64 matrix = FP64 vector rate (half the
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 RF_SCALE = 1.5 ** 15           # mid-ladder RF (value does not change the work)
 RAMP_MS = 2.0                  # untimed launches of the same kernel before a clock starts: the GPU's clocks ramp under load
+TRIAL_STEPS = 2000             # at most this many launches per untimed trial of a launch form: beyond 250 steps every
+                               # call replays the same 250-launch graph, so a longer trial decides nothing new
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs writes at most this much (64 MB with room for the .npy headers)
 
 
 def bytes_alg(B, N, D, NPest, N_data, L):
@@ -204,6 +212,25 @@ def event_timed(pb, rf, steps):
     while ms < RAMP_MS:
         ms += pb.eval_timed(rf, steps)
     return pb.eval_timed(rf, steps) * 1e-3 / steps
+
+
+def dump_outputs(path, pb):
+    """--dump-outputs: what the last timed step left on the device for a caller (va_read_eval_outputs) as float64
+    DIR/A.npy, me.npy, fe.npy (B,) and grad.npy (B, n_var).  A gradient larger than DUMP_BYTES allows is written as
+    grad_sample.npy (B, k): k of its columns, chosen by a fixed seed, their indices in grad_columns.npy."""
+    A, me, fe, g = pb.read_eval_outputs()
+    out = {"A": A, "me": me, "fe": fe}
+    room = DUMP_BYTES // 8 - 3 * len(A)
+    if g.size <= room:
+        out["grad"] = g
+    else:
+        k = room // (g.shape[0] + 1)
+        cols = np.sort(np.random.RandomState(0).choice(g.shape[1], k, replace=False))
+        out["grad_sample"] = g[:, cols]
+        out["grad_columns"] = cols.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def extra_c4(device, steps=60):
@@ -437,26 +464,29 @@ def timed_steps(pb, rf, steps, warmup, A, dist, world, torch, barrier, graph_fix
     # launches): a graph replay starts ~15-20 us after the call and then runs back to back, plain launches start at once
     # and stay device-bound above ~4 us per kernel -- for a handful of steps the plain form ends first.  Both are tried
     # untimed and the faster one is timed; either way every launch is the same kernel.
+    # (trials of at most TRIAL_STEPS launches keep the untimed part of a long run short; up to that many steps they are
+    # the timed call itself)
+    trial = min(steps, TRIAL_STEPS)
     ramp, ramp_ms, best = 0, 0.0, {}
     for mode in ((1, 0) if graph_fixed is None else (int(graph_fixed),)):
         pb.tune(graph=mode)
         pb.eval_timed_prepare(rf, steps)
-        pb.eval_timed(rf, steps); ramp += steps
+        pb.eval_timed(rf, trial); ramp += trial
         w = []
         for _ in range(3):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            ramp_ms += pb.eval_timed(rf, steps)
+            ramp_ms += pb.eval_timed(rf, trial)
             torch.cuda.synchronize()
             w.append(time.perf_counter() - t0)
-            ramp += steps
+            ramp += trial
         best[mode] = min(w)
     mode = min(best, key=best.get)
     pb.tune(graph=mode)
     pb.eval_timed_prepare(rf, steps)
     while ramp < max(warmup, 1) or ramp_ms < RAMP_MS:
-        ramp_ms += pb.eval_timed(rf, steps)              # (same chunk as the timed call: its graph is replayed, not rebuilt)
-        ramp += steps
+        ramp_ms += pb.eval_timed(rf, trial)              # (same chunk as the timed call: its graph is replayed, not rebuilt)
+        ramp += trial
     barrier()
     t0 = time.perf_counter()
     kernel_ms = pb.eval_timed(rf, steps)                 # HIP events on the launch stream
@@ -499,6 +529,8 @@ def nnet_main(args, rank, local_rank, world, dist, torch):
     wall, kernel_ms, gather_ms, ramp, launch_mode = timed_steps(pb, rf, args.steps, args.warmup, A, dist, world, torch, barrier)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pb)
     # three products per layer transition: Z = X W^T, dX = delta W, dW = delta^T X
     flops = B * M * float(np.sum(3 * 2 * s[1:] * s[:-1]))
     balg = 8 * (B * (2 * (M * int(np.sum(s)) + len(Pidx)) + 3) + din.size + dout.size)
@@ -521,7 +553,7 @@ def nnet_main(args, rank, local_rank, world, dist, torch):
                      "hbm_frac_of_8TBs": balg / ks / 1e9 / HBM_PEAK_GBS},
         "cpu_baseline": None,
     }
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import va_nnet_oracle as vno
         from threadpoolctl import threadpool_limits
@@ -562,7 +594,7 @@ def ladder_mode(args, pb0, XP, P, D, N, B, Y, Lidx, device):
                       "A_final_median": float(np.median(r["A"][:, -1])),
                       "k_final_median": float(np.median(r["pest"][:, -1, 0])),
                       "status_counts": np.bincount(r["status"].ravel(), minlength=3).tolist()}), flush=True)
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         # the same ladder for ONE of these seeds by the C oracle (vao_anneal: restated L-BFGS-B +
         # fused forward/adjoint) on one host core -- the reference's execution model
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -628,8 +660,14 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS) + sorted(NNET_WORKLOADS) + ["mnist_shape"])
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra sub-records (C4 shape, C3 ladder)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the result line's headline figure does not need: the CPU baselines and, for c3 "
+                         "on 1 GPU, the extra sub-records (each takes runs of its own; a plain run does neither)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra sub-records (C4 shape, C3 ladder, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (A, me, fe, gradient of rank 0's seeds) "
+                         "as DIR/<name>.npy, float64, at most 64 MB (a larger gradient: a fixed seeded sample of its columns)")
     ap.add_argument("--tile-rows", type=int, default=0)
     ap.add_argument("--mode", default="eval", choices=["eval", "ladder"],
                     help="eval: the contract line (batched A/gradA launches); ladder: a whole "
@@ -657,6 +695,8 @@ def main():
         ap.error("--gpus must be >= 1")
     if args.share_gpu and args.backend != "gloo":
         ap.error("--share-gpu needs --backend gloo")
+    if args.dump_outputs and (args.mode != "eval" or args.workload == "mnist_shape"):
+        ap.error("--dump-outputs writes the outputs of the timed evaluations (--mode eval, not mnist_shape)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks (one process per GPU) as CHILD processes of a
@@ -735,6 +775,8 @@ def main():
     wall, kernel_ms, gather_ms, ramp, launch_mode = timed_steps(pb, RF_SCALE, args.steps, args.warmup, A, dist, world, torch, barrier, tune.get("graph"))
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, pb)
         balg = bytes_alg(B, N, D, 1, N, len(Lidx))
         kern_s = kernel_ms * 1e-3 / args.steps
         achieved = balg / kern_s / 1e9
@@ -759,11 +801,11 @@ def main():
                          "kernel_us": kern_s * 1e6, "bytes_alg_per_launch": balg},
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(D, N, Y, Lidx, XP, P)
             out["cpu_baseline_all"] = cpu_baseline_all(D, N, Y, Lidx, XP, P)
             out["cpu_baseline_numpy"] = cpu_baseline_numpy(D, N, Y, Lidx, XP, P)
-        if world == 1 and args.workload == "c3" and not args.no_extra:
+        if world == 1 and args.workload == "c3" and args.full and not args.no_extra:
             pb.close()
             out["extra"] = {"ladder": extra_ladder(local_rank, D, N, B, Y, Lidx, XP, P),
                             "ladder_c1": extra_ladder_small(local_rank, 200), "ladder_c2": extra_ladder_small(local_rank, 1000),

@@ -56,3 +56,44 @@ def test_env_switches_are_recorded():
     r = run(["--dry-run"], env={"VA_SOMETHING": "1", "VARANNEAL_AMD_LIB_X": "0", "UNRELATED": "x"})
     rec = last_json(r.stdout)
     assert rec["config"]["env"] == {"VARANNEAL_AMD_LIB_X": "0", "VA_SOMETHING": "1"}
+
+
+def test_dump_outputs_stay_under_64_mb(tmp_path, monkeypatch):
+    """--dump-outputs writes float64 arrays; a gradient larger than the budget is a fixed seeded sample of its columns
+    (the same columns on every run) with their indices beside it"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Handle(object):
+        def __init__(self, B, n):
+            r = np.random.RandomState(3)
+            self.out = r.randn(B), r.randn(B), r.randn(B), r.randn(B, n)
+
+        def read_eval_outputs(self):
+            return self.out
+    assert bench.DUMP_BYTES <= 64 * 10 ** 6
+    pb = Handle(4, 50)
+    bench.dump_outputs(str(tmp_path / "whole"), pb)
+    for name, v in zip(("A", "me", "fe", "grad"), pb.out):
+        got = np.load(str(tmp_path / "whole" / (name + ".npy")))
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 500)
+    pb = Handle(4, 5000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), pb)
+        files = sorted(os.listdir(str(tmp_path / d)))
+        assert files == ["A.npy", "fe.npy", "grad_columns.npy", "grad_sample.npy", "me.npy"]
+        assert sum(np.load(str(tmp_path / d / f)).nbytes for f in files) <= bench.DUMP_BYTES
+    cols = np.load(str(tmp_path / "s1" / "grad_columns.npy"))
+    sample = np.load(str(tmp_path / "s1" / "grad_sample.npy"))
+    assert cols.dtype == np.float64 and len(np.unique(cols)) == len(cols) == sample.shape[1] > 0
+    assert np.array_equal(sample, pb.out[3][:, cols.astype(np.int64)])
+    assert np.array_equal(cols, np.load(str(tmp_path / "s2" / "grad_columns.npy")))
+
+
+def test_dump_outputs_only_where_there_are_timed_evaluations():
+    r = run(["--mode", "ladder", "--dump-outputs", "unused", "--dry-run"])
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+    r = run(["--full", "--dry-run"])
+    assert r.returncode == 0

@@ -657,6 +657,27 @@ def test_bench_two_ranks_share_the_gpu():
     assert rec["ms_per_step"] * 1e3 >= 0.9 * rec["roofline"]["kernel_us"] and rec["config"]["final_gather_ms"] > 0.0
 
 
+def test_bench_dump_outputs_are_what_the_timed_steps_computed(capi, tmp_path):
+    """a plain `bench.py --dump-outputs DIR` run times exactly --steps evaluations, measures nothing else, and leaves in
+    DIR the A, me, fe and gradient of every seed that va_action_grad gives for the same seeded inputs, bit for bit"""
+    import json, os, subprocess, sys
+    import bench
+    from varanneal_amd import twin
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["steps"] == 30 and rec["ms_per_step"] > 0.0 and rec["cpu_baseline"] is None and "extra" not in rec
+    w = bench.WORKLOADS["c3"]
+    Y, Lidx, XP, P = bench.make_inputs(w["D"], w["N"], w["B"], 0)
+    with capi.Problem(w["B"], w["D"], w["N"], Y, Lidx, twin.DT, 4.0, 4e-6, P, [0], disc="trapezoid") as pb:
+        want = pb.action_grad(XP, bench.RF_SCALE)
+    for name, v in zip(("A", "me", "fe", "grad"), want):
+        got = np.load(str(tmp_path / (name + ".npy")))
+        assert got.dtype == np.float64 and np.array_equal(got, v), name
+
+
 @pytest.mark.parametrize("name", ["g4_c1_trapezoid_N200", "g4_shipped_SH_N161"])
 def test_every_rung_from_the_references_own_start_point(capi, golden_ladders, name):
     """Rung-local parity against the REFERENCE itself (tests/golden/ladder_paths.npz: the minimiser its own anneal() +

@@ -2,7 +2,7 @@
 # usage: tools/profiles.sh <tag>   -- collect a round's evidence into gpurun_out/profiles_<tag>/ (copy what is to be
 # judged into profiles/ afterwards).  Counter passes run on their own, with --kernel-trace only (tools/pmc.sh, tools/pmc_mem.sh).
 tag=$1; out=gpurun_out/profiles_$tag; mkdir -p $out; export TMPDIR=/tmp
-python bench.py > $out/bench_c3.json 2> $out/bench_c3.err; cut -c1-300 $out/bench_c3.json
+python bench.py --full > $out/bench_c3.json 2> $out/bench_c3.err; cut -c1-300 $out/bench_c3.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_eval -- python3 bench.py --steps 500 --warmup 50 --no-cpu --no-extra > $out/trace_eval.log 2>&1
 cp $out/trace_eval/*/*kernel_stats.csv $out/eval_c3_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_c4 -- python3 bench.py --workload c4 --steps 200 --warmup 20 --no-cpu --no-extra > $out/bench_c4_traced.json 2> $out/trace_c4.log
