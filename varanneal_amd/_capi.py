@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VARANNEAL_AMD_LIB", os.path.join(_HERE, "libvaranneal_amd.so"))   # (env: diagnostic builds)
 
 VA_OK = 0
+VA_EUNSUPPORTED = -4
 ABI_VERSION = 12         # VA_ABI_VERSION of include/varanneal_amd.h
 ERRNAMES = {-1: "VA_EINVAL", -2: "VA_ENOMEM", -3: "VA_EHIP", -4: "VA_EUNSUPPORTED", -5: "VA_ESTATE"}
 DISC = {"euler": 0, "trapezoid": 1, "SimpsonHermite": 2, "forwardmap": 3}
@@ -33,6 +34,12 @@ class VaError(RuntimeError):
     def __init__(self, code, msg):
         RuntimeError.__init__(self, "%s (%d): %s" % (ERRNAMES.get(code, "VA_E?"), code, msg))
         self.code = code
+
+
+class VaUnsupported(VaError, NotImplementedError):
+    """VA_EUNSUPPORTED: a case the library does not implement (the message names why), e.g. a model past 128 parameters
+    on a problem its column-parameter form cannot run.  Still a VaError; a NotImplementedError as well, like every
+    unsupported case of the Python layer."""
 
 
 class ProblemDesc(C.Structure):
@@ -234,7 +241,7 @@ EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_mo
 
 def check(rc):
     if rc != VA_OK:
-        raise VaError(rc, lib().va_last_error().decode("utf-8", "replace"))
+        raise (VaUnsupported if rc == VA_EUNSUPPORTED else VaError)(rc, lib().va_last_error().decode("utf-8", "replace"))
 
 
 def eval_plan(batch, D, N_model, disc, ne, ghost=0, rm_array=False, rm_full=False, rf_array=False, rf_full=False,

@@ -15,7 +15,10 @@ csrc/va_user_rhs.hip into a shared object that va_rhs_load_module() registers.  
 no interpreter at evaluation time.
 
 Limits: `f` must be traceable (no data-dependent Python branching on x/p; NumPy ufuncs
-exp/log/tanh/... and arithmetic are fine); NP <= 24.  Before use the generated
+exp/log/tanh/... and arithmetic are fine).  Parameters: up to 128 on the flat kernel, up
+to 24 on the column-run kernels; a model in column-parameter form (colparam_form: at most
+24 shared scalars and a few per-column vectors of length D, e.g. a forcing per site) takes
+any number on the column-run kernels k_eval4 / k_eval5.  Before use the generated
 expressions are checked numerically against `f` itself on random inputs.
 """
 import hashlib
@@ -30,6 +33,7 @@ CACHE = os.environ.get("VARANNEAL_AMD_RHS_CACHE", os.path.join(_HERE, "_rhs_cach
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 MAX_NP = 128           # RHS_BIG_NP of csrc/va_core.h (the flat kernel); the tuned column / ghosted forms take up to MAX_NP_TUNED
 MAX_NP_TUNED = 24      # RHS_MAX_NP
+MAX_NCV = 4            # CP_VMAX: per-column parameter vectors of a column-parameter form
 
 
 def _sympy():
@@ -322,8 +326,10 @@ def _uniform_flat(exprs, syms, D, NP, pr0):
     return out
 
 
-def generate_header(exprs, syms, D, NP, nstim, name="user", col=None, ghost=None, lin=None):
-    """lin = (A0, rest) from linear_split: the struct then describes `rest` and carries the tables of A0"""
+def generate_header(exprs, syms, D, NP, nstim, name="user", col=None, ghost=None, lin=None, colp=None):
+    """lin = (A0, rest) from linear_split: the struct then describes `rest` and carries the tables of A0.
+    colp: column_form(..., cp=colparam_form(...)), the column-parameter form.  Past MAX_NP parameters the flat struct is
+    a stub (FLAT = false): no flat kernel exists for such a model."""
     sp = _sympy()
     pr = _printer()
     if lin is not None:
@@ -347,17 +353,25 @@ def generate_header(exprs, syms, D, NP, nstim, name="user", col=None, ghost=None
         out.append("    static constexpr int LIN_DP = %d;" % DP)
         out.append("    static VA_HD const double *lin_A0() { return va_lin_A0; }")
         out.append("    static VA_HD const double *lin_A0T() { return va_lin_A0T; }")
-    uni = _uniform_flat(exprs, syms, D, NP, pr) if D >= 8 else None
-    if uni is not None:
-        out += uni
+    if NP > MAX_NP:
+        out.append("    static constexpr bool FLAT = false;     // more parameters than the flat kernel carries: column-parameter form only")
     else:
-        _switch_flat(out, exprs, syms, D, NP, pr, sv)
+        uni = _uniform_flat(exprs, syms, D, NP, pr) if D >= 8 else None
+        if uni is not None:
+            out += uni
+        else:
+            _switch_flat(out, exprs, syms, D, NP, pr, sv)
     out.append("};")
     if col is not None:
         out.append("// the same model in column form (codegen.column_form): %s"
                    % ("translation-invariant stencil, offsets %s" % col["offsets"] if col["uniform"] else "dense, switch on the column"))
         out.append("#define VA_USER_COL 1")
         out.append(col["text"])
+    if colp is not None:
+        out.append("// the same model in column-parameter form (codegen.colparam_form): offsets %s, %d shared scalar(s), %d vector(s)"
+                   % (colp["offsets"], colp["S"], colp["V"]))
+        out.append("#define VA_USER_COLP 1")
+        out.append(colp["text"])
     if ghost is not None:
         out.append("// the same stencil in ghosted column form (codegen.ghost_form): offsets %s, %d ghost columns"
                    % (ghost["offsets"], ghost["GHOST"]))
@@ -453,7 +467,7 @@ def _local_printer(xmap):
     return P()
 
 
-def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None):
+def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None, cp=None):
     """The model in the form the wave-private column-run kernel wants (csrc/va_tile4.h), or None.
 
     A lane owns ONE state column i of a run of time rows; it reads its own value and NB neighbour
@@ -462,9 +476,14 @@ def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None):
     model fit: (a) translation-invariant stencils (every f_i is f_0 shifted cyclically, e.g. Lorenz-96),
     where the neighbours are fixed column offsets and the code has one path; (b) small systems (D <= 8,
     e.g. the tutorial's NaKL neuron) with any coupling, where every other column is a neighbour and the
-    code switches on the column.  Products that are constant multiples of one another are exchanged once."""
+    code switches on the column.  Products that are constant multiples of one another are exchanged once.
+    cp: colparam_form's result -- the struct is then RhsUserColP, written from the reindexed f_0, whose f / scatter /
+    pgrad also take the lane's own vector entries pv[] (and pgrad adds their partials to accv[])."""
     sp = _sympy()
     xs, ps = list(syms["x"]), list(syms["p"])
+    pvs = []
+    if cp is not None:
+        exprs, ps, pvs, NP, uniform = [cp["f0"]] * D, cp["ps"], cp["pv"], cp["S"], True
     uses_t = any(e.has(syms["t"]) for e in exprs)
 
     uniform = _translation_invariant(exprs, xs, D) if uniform is None else uniform
@@ -488,6 +507,8 @@ def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None):
             offs = sorted(offset_set)
             if 0 < len(offs) <= 8 and len(set(o % D for o in offs)) == len(offs):
                 period = P
+    if cp is not None and not uniform:
+        return None                                   # (a column-parameter form is a stencil: neighbours at fixed offsets)
     if not uniform and period is None:
         if D > max_dense or D < 2:
             return None
@@ -500,6 +521,9 @@ def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None):
         xmap = {xs[i]: "x0"}
         for k, o in enumerate(offs):
             xmap[xs[(i + o) % D]] = "xn[%d]" % k
+        if cp is not None:
+            xmap.update({s: "p[%d]" % k for k, s in enumerate(ps)})
+            xmap.update({s: "pv[%d]" % k for k, s in enumerate(pvs)})
         return _local_printer(xmap)
 
     rows = [0] if uniform else (list(range(period)) if period else list(range(D)))
@@ -527,8 +551,10 @@ def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None):
         e_src = reps
     else:
         NE, e_src = NB, list(range(NB))
-    out.append("struct RhsUserCol {")
+    out.append("struct RhsUserColP {" if cp is not None else "struct RhsUserCol {")
     out.append("    static constexpr int NP = %d, D = %d, NSTIM = %d, NB = %d, NE = %d, NG = %d;" % (NP, D, nstim, NB, NE, NB))
+    if cp is not None:
+        out.append("    static constexpr int NCV = %d;          // vectors: entry i of each belongs to column i (pv[])" % len(pvs))
     # rows of an edge tile that do not exist are evaluated at x = 0 with a zero adjoint: their products are exact
     # zeros on their own when every expression is polynomial in x; otherwise (1/x, log x ...) the kernel selects
     poly = all(e.is_polynomial(*xs) for e in exprs)
@@ -538,8 +564,9 @@ def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None):
     out.append("    static VA_HD constexpr int nb_off(int k) { return %s; }" % chain(offs))
     out.append("    static VA_HD constexpr int g_e(int k) { return %s; }" % chain(slot_of))
     out.append("    static VA_HD constexpr int g_off(int k) { return %s; }" % chain([-o for o in offs]))
-    sig = "int col, double x0, const double *xn, const double *p, double t, const double *st"
-    unused = "(void)col; (void)x0; (void)xn; (void)p; (void)t; (void)st;"
+    pvarg = ", const double *pv" if cp is not None else ""
+    sig = "int col, double x0, const double *xn, const double *p%s, double t, const double *st" % pvarg
+    unused = "(void)col; (void)x0; (void)xn; (void)p; (void)t; (void)st;" + (" (void)pv;" if cp is not None else "")
 
     def emit_switch(body_for_row, default):
         if uniform:
@@ -558,7 +585,7 @@ def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None):
     out.append("        return r;")
     out.append("    }")
     # scatter
-    out.append("    static VA_HD void scatter(int col, double s, double x0, const double *xn, const double *p, double t, const double *st, double *e, double &diag)")
+    out.append("    static VA_HD void scatter(int col, double s, double x0, const double *xn, const double *p%s, double t, const double *st, double *e, double &diag)" % pvarg)
     out.append("    {")
     out.append("        %s (void)s;" % unused)
 
@@ -583,9 +610,10 @@ def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None):
     terms = " + ".join(term(k) for k in range(NB))
     out.append("    static VA_HD double gather(const double *r) { return %s; }" % terms)
     # pgrad
-    out.append("    static VA_HD void pgrad(int col, double s, double x0, const double *xn, const double *p, double t, const double *st, double *acc)")
+    out.append("    static VA_HD void pgrad(int col, double s, double x0, const double *xn, const double *p%s, double t, const double *st, double *acc%s)"
+               % (pvarg, ", double *accv" if cp is not None else ""))
     out.append("    {")
-    out.append("        %s (void)s; (void)acc;" % unused)
+    out.append("        %s (void)s; (void)acc;%s" % (unused, " (void)accv;" if cp is not None else ""))
 
     def pg(i):
         pr = local_printer(i)
@@ -594,13 +622,73 @@ def column_form(exprs, syms, D, NP, nstim, max_dense=8, uniform=None):
             dk = sp.diff(exprs[i], ps[k])
             if dk != 0:
                 parts.append("{ %s }" % _emit_case(pr, s_sym * dk, "acc[%d] += %%s;" % k))
+        for k, v in enumerate(pvs):
+            dk = sp.diff(exprs[i], v)
+            if dk != 0:
+                parts.append("{ %s }" % _emit_case(pr, s_sym * dk, "accv[%d] += %%s;" % k))
         return " ".join(parts)
     out += emit_switch(pg, "")
     out.append("    }")
     out.append("};")
+    if cp is not None:
+        # (host side: the loader reads the map through va_user_colp_map, csrc/va_user_rhs.hip)
+        out.append("static const int va_colp_sidx[%d] = {%s};" % (max(1, cp["S"]), ", ".join(str(k) for k in cp["sidx"]) or "0"))
+        out.append("static const int va_colp_vidx[%d] = {%s};" % (cp["V"] * D, ", ".join(str(int(k)) for k in np.ravel(cp["vidx"]))))
     xl, xr = max([0] + [-o for o in offs]), max([0] + offs)
-    return dict(text="\n".join(out), uniform=uniform, period=period, offsets=offs, NE=NE, NB=NB, reach=(xl, xr, xr, xl),
-                autonomous=not uses_t and nstim == 0)
+    res = dict(text="\n".join(out), uniform=uniform, period=period, offsets=offs, NE=NE, NB=NB, reach=(xl, xr, xr, xl),
+               autonomous=not uses_t and nstim == 0)
+    if cp is not None:
+        res.update(S=cp["S"], V=cp["V"], sidx=list(cp["sidx"]), vidx=np.array(cp["vidx"]))
+    return res
+
+
+def colparam_form(exprs, syms, D, NP, max_ncv=MAX_NCV, max_shared=MAX_NP_TUNED):
+    """The model's parameters split into shared scalars and per-column vectors, or None.
+
+    A shared scalar enters every f_i (or none); a vector entry enters exactly one f_i, that of its column.  Every
+    column must own the same number V (1 <= V <= max_ncv) of entries; the v-th vector is made of the v-th entry of each
+    column, and a vector's entries, taken in parameter-index order, belong to columns 0, 1, ..., D-1 (contiguous blocks
+    p[vD + i] and interleaved layouts p[Vi + v] both are).  The model has the form when every f_i is f_0 with the state
+    indices shifted cyclically by i and every vector entry of column 0 replaced by that of column i -- translation
+    invariance once the parameters are reindexed (_translation_invariant for the state alone).
+    Returns dict(S, V, sidx [S] global indices of the shared scalars, vidx [V][D] global index of vector v's entry of
+    column i, f0 = f_0 with shared scalar j as symbol ps[j] and the vectors' column-0 entries as pv[v], ps, pv)."""
+    sp = _sympy()
+    if D < 3 or NP < D:
+        return None
+    xs, psym = list(syms["x"]), list(syms["p"])
+    pidx = {q: k for k, q in enumerate(psym)}
+    rows_of = [[] for _ in range(NP)]
+    for i, e in enumerate(exprs):
+        for q in e.free_symbols:
+            if q in pidx:
+                rows_of[pidx[q]].append(i)
+    shared, percol = [], [[] for _ in range(D)]
+    for k in range(NP):
+        r = rows_of[k]
+        if len(r) == 1:
+            percol[r[0]].append(k)
+        elif len(r) == D or len(r) == 0:
+            shared.append(k)
+        else:
+            return None                              # a parameter of some columns but not all
+    V = len(percol[0])
+    if V == 0 or V > max_ncv or len(shared) > max_shared or any(len(c) != V for c in percol):
+        return None
+    vidx = np.array(percol, dtype=np.int64).T       # [V][D]
+    if D > 1 and np.any(np.diff(vidx, axis=1) <= 0):
+        return None                                  # entry i of a vector must belong to column i
+    for i in range(1, D):
+        rep = {xs[j]: xs[(j + i) % D] for j in range(D)}
+        rep.update({psym[vidx[v][0]]: psym[vidx[v][i]] for v in range(V)})
+        e = exprs[0].xreplace(rep)
+        if e != exprs[i] and sp.simplify(e - exprs[i]) != 0:
+            return None
+    ps = list(sp.symbols("cps0:%d" % max(len(shared), 1), real=True))[:len(shared)]
+    pv = list(sp.symbols("cpv0:%d" % V, real=True))
+    sub = {psym[k]: ps[j] for j, k in enumerate(shared)}
+    sub.update({psym[vidx[v][0]]: pv[v] for v in range(V)})
+    return dict(S=len(shared), V=V, sidx=shared, vidx=vidx, f0=exprs[0].xreplace(sub), ps=ps, pv=pv)
 
 
 def ghost_form(exprs, syms, D, NP, nstim, uniform=None):
@@ -747,21 +835,47 @@ def build_module(header_text, verbose=False, col_variant=None, compile=True):
     return so, hdr
 
 
-def module_for(f, D, NP, nstim=0, stim_ndim=1, verbose=False, p_rows=False, col_variant=None, compile=True, linear=True):
-    """trace + check + generate + build.  Returns dict(so=, header=, exprs=, col=).
+def _ask_variant(col_variant, ne, ghost, reach):
+    """call module_for's col_variant callback: one of three arguments also gets the column form's reaches, or None when
+    the form is not one the streaming kernel can run (non-uniform, explicit time, stimulus)"""
+    import inspect
+    try:
+        three = len(inspect.signature(col_variant).parameters) >= 3
+    except (TypeError, ValueError):
+        three = False
+    return col_variant(ne, ghost, reach) if three else col_variant(ne, ghost)
+
+
+def module_for(f, D, NP, nstim=0, stim_ndim=1, verbose=False, p_rows=False, col_variant=None, compile=True, linear=True,
+               colparams=None):
+    """trace + check + generate + build.  Returns dict(so=, header=, exprs=, col=, colp=).
     col_variant: None, or a callable (NE, GHOST[, reach]) -> (eval kernel 3 | 4 | 5, disc, K, w) or None (as
     _capi.eval_plan returns it) naming the instantiation of a column-run kernel to compile for a model that has
     a column form (NE products per element; 0 = none) and / or a ghosted form (GHOST columns; 0 = none).
-    linear=False keeps a dense constant linear part in the element-wise code (linear_split; for comparisons)."""
-    if NP > MAX_NP:
+    linear=False keeps a dense constant linear part in the element-wise code (linear_split; for comparisons).
+    colparams: True asks for the column-parameter form (colparam_form: shared scalars + per-column vectors) in place
+    of the column / ghosted forms; None (default) asks for it past MAX_NP parameters only, False never.  The form, when the
+    model has it, comes back as colp= (col / ghost stay None) and the callback's column-run instantiation is of it."""
+    if NP > MAX_NP and (p_rows or colparams is False):
         raise NotImplementedError("right-hand sides with more than %d parameters" % MAX_NP)
     exprs, syms = trace(f, D, NP, nstim, stim_ndim, p_rows)
     check_against(f, exprs, syms, D, NP, nstim, stim_ndim, p_rows=p_rows)
-    col = ghost = None
+    col = ghost = colp = None
     variant = None
     if p_rows and NP > MAX_NP_TUNED:
         raise NotImplementedError("time-dependent parameters: at most %d of them" % MAX_NP_TUNED)
-    if col_variant is not None and not p_rows and NP <= MAX_NP_TUNED:      # (many parameters: the flat kernel only)
+    cpf = None
+    if (colparams if colparams is not None else NP > MAX_NP) and not p_rows:
+        cpf = colparam_form(exprs, syms, D, NP)
+        colp = column_form(exprs, syms, D, NP, nstim, cp=cpf) if cpf is not None else None
+    if NP > MAX_NP and colp is None:
+        raise NotImplementedError("right-hand sides with more than %d parameters" % MAX_NP)
+    if colp is not None:
+        if col_variant is not None:
+            variant = _ask_variant(col_variant, colp["NE"], 0, colp["reach"] if colp["autonomous"] else None)
+            if variant is not None and variant[0] not in (4, 5):
+                variant = None
+    elif col_variant is not None and not p_rows and NP <= MAX_NP_TUNED:      # (many parameters: the flat kernel only)
         uniform = _translation_invariant(exprs, list(syms["x"]), D)
         # column form: k_eval4 (D <= 64: stencils and small dense systems) or, for stencils, the streaming k_eval5
         col = column_form(exprs, syms, D, NP, nstim, uniform=uniform)          # (None when the model has no such form)
@@ -769,25 +883,19 @@ def module_for(f, D, NP, nstim=0, stim_ndim=1, verbose=False, p_rows=False, col_
         variant = None
         if col or ghost:
             ne, gh = (col["NE"] if col else 0), (ghost["GHOST"] if ghost else 0)
-            import inspect
-            try:
-                three = len(inspect.signature(col_variant).parameters) >= 3
-            except (TypeError, ValueError):
-                three = False
-            # (a callback of three arguments also gets the column form's reaches, or None when the form is not one
-            # the streaming kernel can run: non-uniform, explicit time, stimulus)
             reach = col["reach"] if (col and (col["uniform"] or col["period"]) and col["autonomous"]) else None
-            variant = col_variant(ne, gh, reach) if three else col_variant(ne, gh)
+            variant = _ask_variant(col_variant, ne, gh, reach)
         if variant is None or variant[0] not in (4, 5):
             col = None
         if variant is None or variant[0] != 3:
             ghost = None
     # no column-run kernel for this model: a dense constant linear part goes to the matrix cores
-    lin = linear_split(exprs, syms, D) if (linear and col is None and ghost is None and not p_rows and NP <= MAX_NP_TUNED) else None
-    text = generate_header(exprs, syms, D, NP, nstim, getattr(f, "__name__", "f"), col=col, ghost=ghost, lin=lin)
+    lin = (linear_split(exprs, syms, D) if (linear and col is None and ghost is None and colp is None and not p_rows
+                                             and NP <= MAX_NP_TUNED) else None)
+    text = generate_header(exprs, syms, D, NP, nstim, getattr(f, "__name__", "f"), col=col, ghost=ghost, lin=lin, colp=colp)
     so, hdr = build_module(text, verbose, variant, compile)
     return dict(so=so, header=hdr, exprs=exprs, text=text, col=col, ghost=ghost, col_variant=variant,
-                lin=(None if lin is None else lin[0]))
+                lin=(None if lin is None else lin[0]), colp=colp)
 
 
 # ---------------------------------------------------------------------------------------------------------

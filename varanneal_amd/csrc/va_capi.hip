@@ -61,6 +61,9 @@ struct UserRhs {
     int (*prepare)(const Dev *) = nullptr;
     int (*seed_kernel)(const Dev *, int, void *) = nullptr;      // the persistent per-seed ladder kernel (va_persist.h), if the module carries it
     int NP = 0, D = 0, NSTIM = 0;
+    // [11] > 0: the column-run instantiation is of the model's column-parameter form (RhsUserColP); its map
+    // (va_user_colp_map): shared scalars S, vectors V, then the global index of each shared scalar and of each vector entry
+    std::vector<int> colp;
 };
 struct UserAct {
     std::string path;
@@ -395,8 +398,9 @@ int alloc_solver_state(va_handle h, int max_beta, int keep_paths)
     TRYA(h->alloc(&dv.S, B * m * ld)); TRYA(h->alloc(&dv.Y, B * m * ld));
     TRYA(h->alloc(&dv.st, B));
     TRYA(h->alloc(&dv.evp, B * dm.nprow * EP_N));
-    dv.npbig = (!h->is_nnet && dm.NPt > RHS_MAX_NP) ? dm.NPt - RHS_MAX_NP : 0;
+    dv.npbig = (!h->is_nnet && !dv.cpv && dm.NPt > RHS_MAX_NP) ? dm.NPt - RHS_MAX_NP : 0;
     if (dv.npbig) TRYA(h->alloc(&dv.evp_big, B * dm.nprow * dv.npbig));
+    if (dv.cpv) TRYA(h->alloc(&dv.evv, B * dm.nprow * dv.cpv));
     TRYA(h->alloc(&dv.upp, B * dm.nchunks * dv.ups));
     TRYA(h->alloc(&dv.dpp, B * dm.nchunks * DP_N));
     TRYA(h->alloc(&h->d_rf, (size_t)max_beta));
@@ -688,13 +692,25 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
         dlclose(u.dl);
         return fail(VA_EINVAL, "%s was built against different headers (Dev %d vs %zu bytes): rebuild it", path, v[3], sizeof(Dev));
     }
-    if (v[0] < 0 || v[0] > RHS_BIG_NP) { dlclose(u.dl); return fail(VA_EUNSUPPORTED, "%s: NP=%d > %d", path, v[0], RHS_BIG_NP); }
     u.NP = v[0]; u.D = v[1]; u.NSTIM = v[2];
     if (info_fn vinfo = (info_fn)dlsym(u.dl, "va_user_variant_info")) {        // (writes 12 ints)
         vinfo(u.var);
         u.launch_var = (void (*)(const Dev *, void *))dlsym(u.dl, "va_user_launch_variant");
         u.prepare_var = (int (*)(const Dev *))dlsym(u.dl, "va_user_prepare_variant");
         if (!u.launch_var || !u.prepare_var) u.var[0] = 0;
+    }
+    if (info_fn cmap = (info_fn)dlsym(u.dl, "va_user_colp_map")) {
+        // (S <= RHS_MAX_NP and V <= CP_VMAX by construction: the generator checks both)
+        u.colp.assign(2 + RHS_MAX_NP + (size_t)CP_VMAX * (u.D > 0 ? u.D : 1), 0);
+        cmap(u.colp.data());
+        u.colp.resize(2 + (size_t)u.colp[0] + (size_t)u.colp[1] * u.D);
+    }
+    if (u.colp.empty()) u.var[11] = 0;
+    // past RHS_BIG_NP parameters a module has no flat kernel: it must carry the column-parameter form (the kernels that
+    // run it are checked problem by problem, va_problem_create)
+    if (v[0] < 0 || (v[0] > RHS_BIG_NP && u.colp.empty())) {
+        dlclose(u.dl);
+        return fail(VA_EUNSUPPORTED, "%s: NP=%d > %d and no column-parameter form", path, v[0], RHS_BIG_NP);
     }
     g_user_rhs.push_back(u);
     *rhs_id = VA_RHS_USER_BASE + (int32_t)g_user_rhs.size() - 1;
@@ -726,6 +742,20 @@ int va_act_load_module(const char *path, int32_t *act_id)
     return VA_OK;
 }
 
+// Why a problem of a module in column-parameter form cannot run that form (the module then has no kernel for it when it has
+// more than RHS_BIG_NP parameters): the first reason that applies.
+static void colp_refusal(const va_problem_desc *d, const UserRhs *u, char *msg, size_t n)
+{
+    if (d->lower && d->upper) snprintf(msg, n, "box bounds (carried by the flat kernel only)");
+    else if (d->p_time_dependent) snprintf(msg, n, "time-dependent parameters");
+    else if (d->rm_kind == 2 || d->rf_kind == 2) snprintf(msg, n, "full RM / RF matrices (flat kernel only)");
+    else if (d->D > 64 && (d->D & 1)) snprintf(msg, n, "odd D = %d > 64 (k_eval3, which has no column-parameter form)", d->D);
+    else if (d->D > 64 && u->var[0] != 5) snprintf(msg, n, "a non-autonomous model (model time or stimulus) on the streaming kernel k_eval5");
+    else if (d->D <= 64 && !tile4_ok(d->D)) snprintf(msg, n, "D = %d fits neither k_eval4 (even D <= 64 filling a wave) nor k_eval5", d->D);
+    else if (d->eval_kernel != 0 && d->eval_kernel != u->var[0]) snprintf(msg, n, "eval_kernel = %d (the module carries kernel %d)", d->eval_kernel, u->var[0]);
+    else snprintf(msg, n, "the module's column-run instantiation does not fit this problem (weights, discretisation or run length): regenerate it");
+}
+
 int va_problem_create(const va_problem_desc *d, va_handle *out)
 {
     if (!d || !out) return fail(VA_EINVAL, "null argument");
@@ -753,7 +783,12 @@ int va_problem_create(const va_problem_desc *d, va_handle *out)
     if (d->rhs == VA_RHS_LORENZ96 && (d->NP != RhsL96::NP || d->D < 4))
         return fail(VA_EINVAL, "Lorenz-96 needs NP=1 and D>=4 (NP=%d D=%d)", d->NP, d->D);
     if (d->n_stim < 0 || (d->n_stim > 0 && !d->stim)) return fail(VA_EINVAL, "n_stim=%d without a stimulus array", d->n_stim);
-    if (d->NPest < 0 || d->NPest > d->NP || d->NP > RHS_BIG_NP) return fail(VA_EINVAL, "bad NP/NPest (%d/%d)", d->NP, d->NPest);
+    // (more than RHS_BIG_NP parameters: a module in column-parameter form only, on k_eval4 / k_eval5 -- checked below)
+    const bool noflat = d->NP > RHS_BIG_NP;
+    if (noflat && !(user && !user->colp.empty()))
+        return fail(VA_EUNSUPPORTED, "NP=%d > %d: only a generated module in column-parameter form (shared scalars + per-column "
+                                     "vectors) carries more, and this model has none", d->NP, RHS_BIG_NP);
+    if (d->NPest < 0 || d->NPest > d->NP) return fail(VA_EINVAL, "bad NP/NPest (%d/%d)", d->NP, d->NPest);
     const bool tdp = d->p_time_dependent != 0;
     // more than RHS_MAX_NP parameters: the flat kernel carries them (their gradient partials in a table of their own)
     const bool bigp = d->NP > RHS_MAX_NP;
@@ -817,13 +852,33 @@ int va_problem_create(const va_problem_desc *d, va_handle *out)
         // was generated); a problem that calls for any other geometry runs the module's flat kernel
         const int *v = user->var;
         dm.lin = v[10] ? 1 : 0;
-        if (bigp) pick_eval_geometry(d, dm, dv.g4, 0, 0);
+        // (a column-parameter form carries any number of parameters: its vectors' partials have a table of their own)
+        const bool cpvar = v[11] > 0 && (v[0] == 4 || v[0] == 5);
+        if (bigp && !cpvar) pick_eval_geometry(d, dm, dv.g4, 0, 0);
         else pick_eval_geometry(d, dm, dv.g4, (v[0] == 4 || v[0] == 5) ? v[4] : 0, v[0] == 3 ? v[5] : 0, v[0] == 5 ? v + 6 : nullptr, &dv.g5, &ystrip_h);
         const bool ws = d->rm_kind == 0 && d->rf_kind == 0 && d->merr_nskip == 1;
         const bool fits = dm.emode == v[0] && v[1] == d->disc &&
                           (dm.emode == 5 ? true : (v[2] == dm.maxr && (dm.emode == 4 ? (v[3] != 0) == ws : v[3] == dm.NT)));
-        if (dm.emode != 1 && fits) { h->user_launch = user->launch_var; h->user_prepare = user->prepare_var; }
+        if (dm.emode != 1 && fits) {
+            h->user_launch = user->launch_var; h->user_prepare = user->prepare_var;
+            if (cpvar) {
+                dv.cps = user->colp[0]; dv.cpv = user->colp[1] * dm.D;
+                dv.cpnsg = dm.emode == 5 ? dv.g5.NSG : 0;
+            }
+        }
         else if (dm.emode != 1) pick_eval_geometry(d, dm, dv.g4, 0, 0);
+        if (noflat && !dv.cpv) {
+            char why[192];
+            colp_refusal(d, user, why, sizeof why);
+            va_problem_destroy(h);
+            return fail(VA_EUNSUPPORTED, "%d parameters: only the column-parameter form on k_eval4 / k_eval5 carries more than %d, "
+                                         "and this problem cannot run it: %s", d->NP, RHS_BIG_NP, why);
+        }
+        if (dm.emode == 4 && dv.cpv > dv.g4.XW) {       // (k_eval4 leaves the vector partials in the wave's x image)
+            const int K = dv.g4.K;
+            va_problem_destroy(h);
+            return fail(VA_EUNSUPPORTED, "runs of %d rows are too short for %d vector entries on k_eval4", K, dv.cpv);
+        }
     }
     if (dm.emode == 4 && (unsigned long long)dm.B * dm.ntiles * dm.ntiles >= (1ull << 32)) {
         va_problem_destroy(h);        // (umulhi by ntiles_magic would no longer be an exact division)
@@ -839,7 +894,8 @@ int va_problem_create(const va_problem_desc *d, va_handle *out)
     dm.cfe = 1.0 / ((double)dm.D * (dm.N - 1));
     dm.rm = d->rm; dm.rf0 = d->rf0;
     dv.ups = UP_OLD + 4 * m; dv.max_beta = max_beta; dv.nbeta = 1;
-    dv.evcols = EP_GP + d->NP <= 8 ? 8 : (EP_GP + d->NP <= 16 ? 16 : 32);
+    const int npcols = dv.cpv ? dv.cps : d->NP;          // (column-parameter form: the shared scalars only)
+    dv.evcols = EP_GP + npcols <= 8 ? 8 : (EP_GP + npcols <= 16 ? 16 : 32);
     // write-through gradient stores pay where the grid is one resident round and the end-of-kernel write-back
     // of 10 MB is on the critical path (C3: -1.3 us); on large grids they cost 10 % (4096 seeds: 446 vs 404 us)
     dv.gaux = h->fold ? 1 : 0;
@@ -956,6 +1012,17 @@ int va_problem_create(const va_problem_desc *d, va_handle *out)
     dv.pp.rm_arr = (d->rm_kind == 1 || warr5) ? rm_d : nullptr;
     dv.pp.rm_full = d->rm_kind == 2 ? rm_d : nullptr; dv.pp.Lidx = lidx_d;
     dv.pp.Pidx = pidx_d; dv.pp.Pfull = P_d;
+    if (dv.cpv) {
+        // column-parameter form: each shared scalar / vector entry -> its global index, then its index in p_est or -1
+        const int NT = dv.cps + dv.cpv;
+        std::vector<int> pest(d->NP, -1), cm(2 * (size_t)NT);
+        for (int k = 0; k < d->NPest; ++k) pest[d->Pidx[k]] = k;
+        for (int j = 0; j < NT; ++j) { cm[j] = user->colp[2 + j]; cm[NT + j] = pest[cm[j]]; }
+        int *cm_d = nullptr;
+        TRY(h->alloc(&cm_d, cm.size()));
+        H2D(cm_d, cm.data(), cm.size(), int);
+        dv.cpmap = cm_d;
+    }
     dv.pp.tmodel = t_d; dv.pp.stim = st_d; dv.pp.nstim = d->n_stim;
 
     // few seeds, short paths: can the whole minimisation live in LDS?  (flat tile phases: any right-hand side, any

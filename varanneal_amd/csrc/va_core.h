@@ -166,6 +166,16 @@ template <int DISC> struct Halo {
 template <class RHS, class = void> struct rhs_linear { static constexpr bool value = false; };
 template <class RHS> struct rhs_linear<RHS, decltype((void)RHS::LINEAR)> { static constexpr bool value = true; };
 
+// Column-parameter form (codegen.colparam_form): besides NP shared scalars the model has NCV vectors of D entries
+// each, and f_i reads entry i of every vector.  The column struct's f / scatter / pgrad then also take the lane's own
+// entries pv[] and pgrad adds their partials to accv[] (va_tile4.h col_f / col_scatter / col_pgrad).
+constexpr int CP_VMAX = 4;
+template <class RHS, class = void> struct rhs_ncv { static constexpr int value = 0; };
+template <class RHS> struct rhs_ncv<RHS, decltype((void)RHS::NCV)> { static constexpr int value = RHS::NCV; };
+// a generated module of more than RHS_BIG_NP parameters has no flat struct: its RhsUser says FLAT = false
+template <class RHS, class = void> struct rhs_flat { static constexpr bool value = true; };
+template <class RHS> struct rhs_flat<RHS, decltype((void)RHS::FLAT)> { static constexpr bool value = RHS::FLAT; };
+
 struct TileCtx {
     double *js = nullptr;        // [T*D] (LDS): J^T s of the dense linear part, device only
     int n0, R, use_d;            // first owned row, rows staged, trial point x + stp*d ?

@@ -73,6 +73,14 @@ struct Dev {
     double *lb_z, *lb_r, *lb_xp, *lb_t, *lb_mat, *lb_dtd;
     int *lb_iwhere;
     Persist pz;
+    // (last: the fields above keep their kernel-argument offsets)
+    // column-parameter form on k_eval4 / k_eval5 (a module's RhsUserColP; 0 / NULL otherwise): cps shared scalars and
+    // cpv = NCV * D vector entries.  cpmap [2][cps + cpv]: the global parameter index of each, then its index in p_est
+    // or -1 (fixed); evv [B][ntiles][cpv]: the vector entries' gradient partials per workgroup; cpnsg: k_eval5's
+    // workgroups per row of strips (only those of a column's strip hold its partials), 0 for k_eval4
+    const int *cpmap;
+    double *evv;
+    int cps, cpv, cpnsg;
 };
 
 // launch wrappers (va_kernels.hip); all asynchronous on `s`

@@ -118,13 +118,72 @@ __device__ __forceinline__ void reduce_eval_block(const Dev &dv, int b, int lane
     }
 }
 
+// Column-parameter form (Dev::cpv > 0): the gradient of the estimated vector entries and their share of the
+// line-search sums, by the WHOLE wave -- one lane per entry, the entry's partials added over the workgroups in tile
+// order (k_eval5: only the tiles of the column's row of strips hold it), then a butterfly over the wave, which leaves
+// bitwise the same sums in every lane.  Written this launch (write-through), read around L1.
+__device__ __forceinline__ void colp_tail(const Dev &dv, int b, int lane, double *ev, int use_d)
+{
+    const Dims &dm = dv.dm;
+    const int S = dv.cps, VD = dv.cpv, NT = S + VD, D = dm.D;
+    double *gt = dv.gt + (size_t)b * dm.ld;
+    const double *d = dv.d + (size_t)b * dm.ld;
+    const double *tb = dv.evv + (size_t)b * dm.ntiles * VD;
+    double gtd = 0.0, gn2 = 0.0, gmax = 0.0;
+    for (int e0 = 0; e0 < VD; e0 += 64) {
+        const int e = e0 + lane;
+        const int k = e < VD ? dv.cpmap[NT + S + e] : -1;
+        if (k < 0) continue;
+        int t0 = 0, ts = 1;
+        if (dv.cpnsg > 0) {
+            const int c = e % D;
+            int s5 = 0;
+            while (s5 + 1 < dv.g5.NS && tile5_c0(D, dv.g5.NS, s5 + 1) <= c) ++s5;
+            t0 = s5 / dv.g5.WPG; ts = dv.cpnsg;
+        }
+        const double g = col_reduce<true>(tb + e, dm.ntiles, VD, t0, ts, false);
+        gt[dm.ND + k] = g;
+        if (use_d) gtd = fma(g, d[dm.ND + k], gtd);
+        gn2 = fma(g, g, gn2);
+        gmax = fmax(gmax, fabs(g));
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        gtd += __shfl_xor(gtd, o, 64);
+        gn2 += __shfl_xor(gn2, o, 64);
+        gmax = fmax(gmax, __shfl_xor(gmax, o, 64));
+    }
+    if (use_d) ev[EP_GTD] += gtd;
+    ev[EP_GN2] += gn2;
+    ev[EP_GMAX] = fmax(ev[EP_GMAX], gmax);
+}
+
 // parameter tail of grad A (sum over tiles of the per-tile parameter partials) and its
-// share of the line-search sums.
+// share of the line-search sums.  CP: the calling kernel may run a column-parameter form (compiled in only there: the
+// extra code costs the other kernels' tails scalar registers)
+template <bool CP = false>
 __device__ __forceinline__ void eval_tail(const Dev &dv, int b, int use_d, double *ev, double stp = 0.0)
 {
     const Dims &dm = dv.dm;
     double *gt = dv.gt + (size_t)b * dm.ld;
     const double *d = dv.d + (size_t)b * dm.ld, *x = dv.x + (size_t)b * dm.ld;
+    if (CP && dv.cpv) {
+        // column-parameter form: the shared scalars only (partial column EP_GP + j for scalar j; colp_tail has done the
+        // vector entries); no bounds on this path
+        const int NT = dv.cps + dv.cpv;
+        for (int j = 0; j < dv.cps; ++j) {
+            const int k = dv.cpmap[NT + j];
+            if (k < 0) continue;
+            double g = 0.0;
+#pragma unroll
+            for (int i = 0; i < RHS_MAX_NP; ++i) g = (j == i) ? ev[EP_GP + i] : g;
+            gt[dm.ND + k] = g;
+            if (use_d) ev[EP_GTD] += g * as_const(d)[dm.ND + k];
+            ev[EP_GN2] += g * g;
+            ev[EP_GMAX] = fmax(ev[EP_GMAX], fabs(g));
+        }
+        return;
+    }
     for (int k = 0; k < dm.NPest; ++k) {
         // (select chain, not ev[EP_GP + idx]: a run-time index would put ev[] -- and with it every wave
         // of the evaluation kernel -- on scratch memory)
@@ -154,7 +213,8 @@ __device__ __forceinline__ void eval_tail(const Dev &dv, int b, int use_d, doubl
 // The tail of one evaluation of seed b, run by ONE whole wave.  `sh`: 512 bytes of LDS private to
 // the calling wave.  SC1: the partial rows were written in this launch (read them around L1).
 // One memory round trip: the partial rows and the seed's state are requested together.
-template <bool SC1>
+// CP: as eval_tail (k_eval4 / k_eval5 of a column-parameter form, and the separate tail kernels).
+template <bool SC1, bool CP = false>
 __device__ __forceinline__ void eval_epilogue(const Dev &dv, int b, int lane, SeedHot *sh, int mode,
                                               const double *ev_ready = nullptr)
 {
@@ -169,8 +229,9 @@ __device__ __forceinline__ void eval_epilogue(const Dev &dv, int b, int lane, Se
         for (int c = 0; c < EP_N; ++c) ev[c] = ev_ready[c];
     } else reduce_eval<SC1>(dv, b, lane, ev);
     if (mode == EPI_FINALIZE) {
+        if (CP && dv.cpv) colp_tail(dv, b, lane, ev, 0);
         if (lane != 0) return;
-        eval_tail(dv, b, 0, ev);
+        eval_tail<CP>(dv, b, 0, ev);
         const double me = ev[EP_ME] * dm.cme, fe = ev[EP_FE] * dm.cfe * as_const(static_cast<const SeedHot *>(dv.st + b))->rf_scale;
         dv.outA[b] = me + fe; dv.outme[b] = me; dv.outfe[b] = fe;
         return;
@@ -183,9 +244,10 @@ __device__ __forceinline__ void eval_epilogue(const Dev &dv, int b, int lane, Se
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (CP && dv.cpv) colp_tail(dv, b, lane, ev, sh->phase == PH_LS);
     if (lane == 0) {
         atomicAdd(dv.n_evals, 1ULL);
-        eval_tail(dv, b, sh->phase == PH_LS, ev, sh->stp);
+        eval_tail<CP>(dv, b, sh->phase == PH_LS, ev, sh->stp);
         SeedResults r;
         r.ame = dv.ame + (size_t)b * dv.max_beta * 3;
         r.pest = nullptr;

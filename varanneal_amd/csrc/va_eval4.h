@@ -44,6 +44,7 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
 
     constexpr int HL = Halo<DISC>::HL, HR = Halo<DISC>::HR, NE = RHS::NE;
     constexpr int NV = EP_GP + RHS::NP;
+    constexpr int NCV = rhs_ncv<RHS>::value;                  // vectors of a column-parameter form (0: none)
     VA_E4_STAMP_SETUP(dv, w);      // (diagnostic builds only: va_measure.h)
     VA_E4_STAMP(0);
     // with D fixed at compile time the whole geometry (and every LDS offset) is constant
@@ -84,7 +85,32 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
     t.c = 2.0 * st->rf_scale * dm.cfe;
     t.xs = xsw; t.es = r2w;
     t.gtg = dv.gt + (size_t)b * dm.ld;
-    {   // parameters (estimated ones from the trial point), all uniform
+    if constexpr (NCV > 0) {
+        // column-parameter form: the shared scalars (uniform) and the lane's own entries of the vectors, each from the
+        // trial point when estimated (cpmap: global index, then index in p_est or -1)
+        const int nt = dv.cps + dv.cpv;
+#pragma unroll
+        for (int k = 0; k < RHS::NP; ++k) {
+            const int ke = as_const(dv.cpmap)[nt + k];
+            double v = as_const(dv.pp.Pfull)[(size_t)b * dm.NP + as_const(dv.cpmap)[k]];
+            if (ke >= 0) {
+                v = as_const(xg)[dm.ND + ke];
+                if (use_d) v = trial(v, stp, as_const(dg)[dm.ND + ke]);
+            }
+            t.p[k] = v;
+        }
+#pragma unroll
+        for (int u = 0; u < NCV; ++u) {
+            const int e = dv.cps + u * D + tx;
+            const int ke = dv.cpmap[nt + e];
+            double v = dv.pp.Pfull[(size_t)b * dm.NP + dv.cpmap[e]];
+            if (ke >= 0) {
+                v = xg[dm.ND + ke];
+                if (use_d) v = trial(v, stp, dg[dm.ND + ke]);
+            }
+            t.pv[u] = v;
+        }
+    } else {   // parameters (estimated ones from the trial point), all uniform
 #pragma unroll
         for (int k = 0; k < RHS::NP; ++k) t.p[k] = as_const(dv.pp.Pfull)[(size_t)b * dm.NP + k];
         for (int k = 0; k < dm.NPest; ++k) {
@@ -96,7 +122,7 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
         }
     }
     T4Regs<K, NE> rg[SUB];
-    ThreadAcc acc;
+    ColAcc<RHS> acc;
     acc.clear();
     if constexpr (WS == 2) {
         // data at every nskip-th model row: the lane walks its rows once, counting data rows; rows without data read as 0
@@ -220,6 +246,16 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
             const double r = (k == EP_GMAX) ? wave_max(acc.v[k]) : wave_sum_mfma(acc.v[k]);
             if (lane == 0) strip[k] = r;
         }
+        if constexpr (NCV > 0) {
+            // the vector entries' partials: the lane's column summed over the wave's runs (lanes tx + a D, in run
+            // order), left in the wave's x image -- dead since the rows phase -- as [NCV][D]
+#pragma unroll
+            for (int u = 0; u < NCV; ++u) {
+                double sv = 0.0;
+                for (int a2 = 0; a2 < g.RW; ++a2) sv += __shfl(acc.v[EP_N + u], a2 * D + tx, 64);
+                if (lane < D) xsw[u * D + lane] = sv;
+            }
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         VA_E4_STAMP(5);
         __builtin_amdgcn_s_barrier();
@@ -230,6 +266,14 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
                 double v = (lane == EP_GMAX) ? fmax(fmax(r0, r1), fmax(r2, r3)) : ((r0 + r1) + r2) + r3;
                 if ((lane == EP_GTD && !use_d) || ((lane == EP_GTD || lane == EP_GN2 || lane == EP_GMAX) && !lsq)) v = 0.0;
                 st_sc1(dv.evp + ((size_t)b * dm.ntiles + tile) * EP_N + lane, v);
+            }
+            if constexpr (NCV > 0) {
+                // the workgroup's row of the vector table: the four waves added in wave order (write-through, as the row above)
+                double *vrow = dv.evv + ((size_t)b * dm.ntiles + tile) * dv.cpv;
+                for (int e = lane; e < NCV * D; e += 64) {
+                    const double r0 = smem[e], r1 = smem[g.WAVE + e], r2 = smem[2 * g.WAVE + e], r3 = smem[3 * g.WAVE + e];
+                    st_sc1(vrow + e, ((r0 + r1) + r2) + r3);
+                }
             }
             if (dv.epi != EPI_NONE) {
                 // the wave has nothing else in flight: the row is acknowledged quickly, and the count
@@ -315,7 +359,7 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
         VA_E4_STAMP(7);
         if (last) {
             if (lane == 0) __hip_atomic_store(dv.cnt_eval + (size_t)b * CNT_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            eval_epilogue<true>(dv, b, lane, reinterpret_cast<SeedHot *>(xsw), dv.epi);
+            eval_epilogue<true, (NCV > 0)>(dv, b, lane, reinterpret_cast<SeedHot *>(xsw), dv.epi);
         }
     }
     VA_E4_STAMP_TAIL(last);        // (wave 0 re-uses slot 1)

@@ -64,6 +64,7 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
     const int b = w / dm.ntiles, tile = w - b * dm.ntiles;
 
     constexpr int NE = RHS::NE, NB = RHS::NB, NG = RHS::NG, NV = EP_GP + RHS::NP;
+    constexpr int NCV = rhs_ncv<RHS>::value;                 // vectors of a column-parameter form (0: none)
     constexpr int P = NSLOT - 1;                              // slots requested ahead of the one in use
     // column geometry: constant when D is
     constexpr Geo5 gcc = tile5_cols_rhs<RHS>(DC > 0 ? DC : 128);
@@ -138,8 +139,33 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
         const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(
             (void *)(dv.gt + (size_t)b * dm.ld), 0, (int)(sizeof(double) * N * D), 0x00020000);
 
-        double p[RHS::NP > 0 ? RHS::NP : 1];
-        {   // parameters (estimated ones from the trial point), all uniform
+        double p[RHS::NP > 0 ? RHS::NP : 1], pv[NCV > 0 ? NCV : 1];
+        if constexpr (NCV > 0) {
+            // column-parameter form (as k_eval4): uniform shared scalars, and the entries of the lane's column -- ghost
+            // lanes included, their f feeds the strip's products
+            const int nt = dv.cps + dv.cpv;
+#pragma unroll
+            for (int k = 0; k < RHS::NP; ++k) {
+                const int ke = as_const(dv.cpmap)[nt + k];
+                double v = as_const(dv.pp.Pfull)[(size_t)b * dm.NP + as_const(dv.cpmap)[k]];
+                if (ke >= 0) {
+                    v = as_const(xg)[dm.ND + ke];
+                    if (use_d) v = trial(v, stp, as_const(dg)[dm.ND + ke]);
+                }
+                p[k] = v;
+            }
+#pragma unroll
+            for (int u = 0; u < NCV; ++u) {
+                const int e = dv.cps + u * D + col;
+                const int ke = dv.cpmap[nt + e];
+                double v = dv.pp.Pfull[(size_t)b * dm.NP + dv.cpmap[e]];
+                if (ke >= 0) {
+                    v = xg[dm.ND + ke];
+                    if (use_d) v = trial(v, stp, dg[dm.ND + ke]);
+                }
+                pv[u] = v;
+            }
+        } else {   // parameters (estimated ones from the trial point), all uniform
 #pragma unroll
             for (int k = 0; k < RHS::NP; ++k) p[k] = as_const(dv.pp.Pfull)[(size_t)b * dm.NP + k];
             for (int k = 0; k < dm.NPest; ++k) {
@@ -196,9 +222,11 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
         double x0p = 0.0, fp = 0.0, qp = 0.0, yp = 0.0, dp = 0.0, wfp = 0.0, wmp = 0.0, xnp[NB];
 #pragma unroll
         for (int k = 0; k < NB; ++k) xnp[k] = 0.0;
-        double fe = 0.0, me = 0.0, gtd = 0.0, gn2 = 0.0, gmax = 0.0, gp[RHS::NP > 0 ? RHS::NP : 1];
+        double fe = 0.0, me = 0.0, gtd = 0.0, gn2 = 0.0, gmax = 0.0, gp[RHS::NP > 0 ? RHS::NP : 1], gpv[NCV > 0 ? NCV : 1];
 #pragma unroll
         for (int k = 0; k < RHS::NP; ++k) gp[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < NCV; ++k) gpv[k] = 0.0;
 
         // finish a row: its direct term and s (the adjoint weight that multiplies df/dx of that row)
         // (WARR) the row about to be finished, modulo nskip: data exist where it is 0
@@ -209,8 +237,8 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
         }
         auto emit_row = [&](double x0, const double *xn, double yv, double dval, double wm, double direct, double s, int orow) {
             double e[NE], diag;
-            RHS::scatter(col, s, x0, xn, p, 0.0, nullptr, e, diag);
-            RHS::pgrad(col, s, x0, xn, p, 0.0, nullptr, gp);
+            col_scatter<RHS>(col, s, x0, xn, p, pv, 0.0, nullptr, e, diag);
+            col_pgrad<RHS>(col, s, x0, xn, p, pv, 0.0, nullptr, gp, gpv);
             double r[NG];
             if constexpr (XDPP) T5Gather<RHS, NG - 1>::run(e, r);
             else {
@@ -281,7 +309,7 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
         // row j enters: f_j, the residual of the interval (j-1, j), and row j-1 is finished; FIRST: only
         // load the state registers
         auto step = [&](const Row &t, bool first, int orow) {
-            const double f = RHS::f(col, t.x0, t.xn, p, 0.0, nullptr);
+            const double f = col_f<RHS>(col, t.x0, t.xn, p, pv, 0.0, nullptr);
             if (!first) {
                 double r;
                 if constexpr (DISC == DISC_TRAPEZOID) r = (t.x0 - x0p) - hdt * (fp + f);
@@ -332,8 +360,8 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
             double q2p = 0.0;                                 // (qp is q1 of the interval behind)
             const double dt3 = dt / 3.0, dt4 = dt / 4.0;
             auto step_sh = [&](const Row &t0, const Row &t1) {
-                const double f0 = RHS::f(col, t0.x0, t0.xn, p, 0.0, nullptr);
-                const double f1 = RHS::f(col, t1.x0, t1.xn, p, 0.0, nullptr);
+                const double f0 = col_f<RHS>(col, t0.x0, t0.xn, p, pv, 0.0, nullptr);
+                const double f1 = col_f<RHS>(col, t1.x0, t1.xn, p, pv, 0.0, nullptr);
                 const double r1 = t1.x0 - x0p - (fp + 4.0 * f0 + f1) * dt3;
                 const double r2 = t0.x0 - (0.5 * (x0p + t1.x0) + (fp - f1) * dt4);
                 const double w1 = WARR ? wfp * r1 : r1, w2 = WARR ? t0.wf * r2 : r2;     // (weight rows m and m+1, as va_tile4.h)
@@ -364,6 +392,8 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
                     fe = 0.0; me = 0.0; gtd = 0.0; gn2 = 0.0; gmax = 0.0;
 #pragma unroll
                     for (int u = 0; u < RHS::NP; ++u) gp[u] = 0.0;
+#pragma unroll
+                    for (int u = 0; u < NCV; ++u) gpv[u] = 0.0;
                 }
                 pos = pos + 1 == NSLOT ? 0 : pos + 1;
                 ppos = ppos + 1 == NSLOT ? 0 : ppos + 1;
@@ -387,6 +417,8 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
             fe = 0.0; me = 0.0; gtd = 0.0; gn2 = 0.0; gmax = 0.0;
 #pragma unroll
             for (int k = 0; k < RHS::NP; ++k) gp[k] = 0.0;
+#pragma unroll
+            for (int k = 0; k < NCV; ++k) gpv[k] = 0.0;
         }
         const int nfull = SR >> 1;                            // slots with two rows of the stream
         int pos = 1 % NSLOT, ppos = (1 + P) % NSLOT;
@@ -417,6 +449,17 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
         acc.v[EP_GMAX] = own ? gmax : 0.0;
 #pragma unroll
         for (int k = 0; k < RHS::NP; ++k) acc.v[EP_GP + k] = own ? gp[k] : 0.0;
+        if constexpr (NCV > 0) {
+            // the vector entries' partials: a strip's own lanes are distinct columns, so the workgroup's row of the
+            // vector table takes each lane's sum as it is (write-through; drained before the workgroup barrier, so
+            // that wave 0's arrival below comes after them)
+            double *vrow = dv.evv + ((size_t)b * dm.ntiles + tile) * dv.cpv;
+            if (own) {
+#pragma unroll
+                for (int u = 0; u < NCV; ++u) st_sc1(vrow + u * D + col, gpv[u]);
+            }
+            VA_WAIT_VM(0);
+        }
     }
 
     // ---- ONE row of partial sums per workgroup (as k_eval4): matrix-pipe wave sums, LDS strip, wave 0 adds
@@ -444,7 +487,7 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
     }
     if (dv.epi == EPI_NONE) return;
     if (arrive_last(dv.cnt_eval + (size_t)b * CNT_STRIDE, (unsigned)dm.ntiles, lane))
-        eval_epilogue<true>(dv, b, lane, reinterpret_cast<SeedHot *>(smem + T4_STRIP), dv.epi);
+        eval_epilogue<true, (NCV > 0)>(dv, b, lane, reinterpret_cast<SeedHot *>(smem + T4_STRIP), dv.epi);
 }
 
 inline size_t eval5_lds_bytes(const Dev &dv)

@@ -169,6 +169,8 @@ hipError_t seed_kernel_builtin(const Dev &dv, bool launch, hipStream_t s) { retu
 constexpr int TAIL_MAX_WAVES = 16;
 static int tail_waves(const Dims &dm) { const int w = (dm.nprow + 127) / 128; return w < 1 ? 1 : (w > TAIL_MAX_WAVES ? TAIL_MAX_WAVES : w); }
 
+// CP: the handle runs a column-parameter form (Dev::cpv): that instantiation alone carries its tail
+template <bool CP>
 __global__ __launch_bounds__(64 * TAIL_MAX_WAVES) void k_ls(const Dev dv)
 {
     __shared__ SeedHot sh;
@@ -179,14 +181,16 @@ __global__ __launch_bounds__(64 * TAIL_MAX_WAVES) void k_ls(const Dev dv)
     if (phase != PH_START && phase != PH_LS) return;
     double ev[EP_N];
     reduce_eval_block(dv, b, lane, wave, nw, part, ev);
-    if (wave == 0) eval_epilogue<false>(dv, b, lane, &sh, EPI_LS, ev);
+    if (wave == 0) eval_epilogue<false, CP>(dv, b, lane, &sh, EPI_LS, ev);
 }
 void launch_ls(const Dev &dv, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_ls, dim3(dv.dm.B), dim3(64 * tail_waves(dv.dm)), 0, s, dv);
+    if (dv.cpv) hipLaunchKernelGGL(k_ls<true>, dim3(dv.dm.B), dim3(64 * tail_waves(dv.dm)), 0, s, dv);
+    else hipLaunchKernelGGL(k_ls<false>, dim3(dv.dm.B), dim3(64 * tail_waves(dv.dm)), 0, s, dv);
 }
 
 // S1 tail: A, me, fe and the parameter tail for a plain evaluation.
+template <bool CP>
 __global__ __launch_bounds__(64 * TAIL_MAX_WAVES) void k_finalize_eval(const Dev dv)
 {
     __shared__ double part[TAIL_MAX_WAVES * 32];
@@ -194,11 +198,12 @@ __global__ __launch_bounds__(64 * TAIL_MAX_WAVES) void k_finalize_eval(const Dev
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
     double ev[EP_N];
     reduce_eval_block(dv, b, lane, wave, nw, part, ev);
-    if (wave == 0) eval_epilogue<false>(dv, b, lane, nullptr, EPI_FINALIZE, ev);
+    if (wave == 0) eval_epilogue<false, CP>(dv, b, lane, nullptr, EPI_FINALIZE, ev);
 }
 void launch_finalize_eval(const Dev &dv, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_finalize_eval, dim3(dv.dm.B), dim3(64 * tail_waves(dv.dm)), 0, s, dv);
+    if (dv.cpv) hipLaunchKernelGGL(k_finalize_eval<true>, dim3(dv.dm.B), dim3(64 * tail_waves(dv.dm)), 0, s, dv);
+    else hipLaunchKernelGGL(k_finalize_eval<false>, dim3(dv.dm.B), dim3(64 * tail_waves(dv.dm)), 0, s, dv);
 }
 
 // reset every seed: phase, ladder position, RF.  rf < 0 -> take rf_ladder[0].

@@ -187,6 +187,7 @@ __global__ __launch_bounds__(PZ_THREADS) void k_seed(const Dev dv)
     const Dims &dm = dv.dm;                 // the persistent image: dm.T = rows per slice, dm.ntiles = G
     constexpr int HL = Halo<DISC>::HL, HR = Halo<DISC>::HR;
     constexpr int K = EP_GP + RHS::NP;      // eval partial columns in use
+    static_assert(K <= EP_N, "k_seed carries at most RHS_MAX_NP parameters: red / ThreadAcc / the exchange rows have EP_N columns");
     constexpr int NT = PZ_THREADS;
     const int G = dm.ntiles, T = dm.T, D = dm.D, m = dm.m, NPe = dm.NPest;
     const int b = blockIdx.x / G, w = blockIdx.x - b * G;
@@ -593,17 +594,23 @@ inline const void *seed_kernel_of(const void *const k[4], int disc)
 // a process that made a cooperative launch under rocprofv3 --kernel-trace dies in the tool's exit handler.  Should the
 // workgroups not all be resident after all (another process holding CUs), the bounded polls end the launch with
 // abort_flag = 1 and the host falls back to the three-launch cycle.
+// A model of more than RHS_MAX_NP parameters (every generated module instantiates this) has no k_seed: refused, never launched.
 template <class RHS>
 inline hipError_t seed_kernel_op(const Dev &dv, bool launch, hipStream_t s)
 {
-    const void *const ks[4] = {(const void *)k_seed<RHS, DISC_EULER>, (const void *)k_seed<RHS, DISC_TRAPEZOID>,
-                               (const void *)k_seed<RHS, DISC_SH>, (const void *)k_seed<RHS, DISC_FWDMAP>};
-    const void *k = seed_kernel_of(ks, dv.dm.disc);
-    const int HL = dv.dm.disc == DISC_SH ? 2 : 1;
-    const size_t lds = 8 * persist_lds_doubles(dv.dm.T, dv.dm.D, dv.dm.L, RHS::NP, dv.dm.NPest, dv.dm.m, HL, dv.dm.ntiles);
-    if (!launch) return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    void *args[1] = {(void *)&dv};
-    return hipLaunchKernel(k, dim3(dv.dm.B * dv.dm.ntiles), dim3(PZ_THREADS), args, lds, s);
+    if constexpr (EP_GP + RHS::NP > EP_N || !rhs_flat<RHS>::value) {
+        (void)dv; (void)launch; (void)s;
+        return hipErrorNotSupported;
+    } else {
+        const void *const ks[4] = {(const void *)k_seed<RHS, DISC_EULER>, (const void *)k_seed<RHS, DISC_TRAPEZOID>,
+                                   (const void *)k_seed<RHS, DISC_SH>, (const void *)k_seed<RHS, DISC_FWDMAP>};
+        const void *k = seed_kernel_of(ks, dv.dm.disc);
+        const int HL = dv.dm.disc == DISC_SH ? 2 : 1;
+        const size_t lds = 8 * persist_lds_doubles(dv.dm.T, dv.dm.D, dv.dm.L, RHS::NP, dv.dm.NPest, dv.dm.m, HL, dv.dm.ntiles);
+        if (!launch) return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        void *args[1] = {(void *)&dv};
+        return hipLaunchKernel(k, dim3(dv.dm.B * dv.dm.ntiles), dim3(PZ_THREADS), args, lds, s);
+    }
 }
 
 }  // namespace va

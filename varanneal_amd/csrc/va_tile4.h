@@ -121,7 +121,33 @@ struct Tile4 {
     double *es;                     // LDS: the wave's product arrays [NE][RW*PITCH]
     double *gtg;
     double p[RHS_MAX_NP];
+    double pv[CP_VMAX];             // column-parameter form: the lane's own entries of the model's vectors
 };
+
+// calls into a column struct, with the lane's vector entries pv / their partials accv for the column-parameter form
+template <class RHS>
+VA_HD double col_f(int col, double x0, const double *xn, const double *p, const double *pv, double t, const double *st)
+{
+    if constexpr (rhs_ncv<RHS>::value > 0) return RHS::f(col, x0, xn, p, pv, t, st);
+    else { (void)pv; return RHS::f(col, x0, xn, p, t, st); }
+}
+template <class RHS>
+VA_HD void col_scatter(int col, double s, double x0, const double *xn, const double *p, const double *pv, double t,
+                       const double *st, double *e, double &diag)
+{
+    if constexpr (rhs_ncv<RHS>::value > 0) RHS::scatter(col, s, x0, xn, p, pv, t, st, e, diag);
+    else { (void)pv; RHS::scatter(col, s, x0, xn, p, t, st, e, diag); }
+}
+template <class RHS>
+VA_HD void col_pgrad(int col, double s, double x0, const double *xn, const double *p, const double *pv, double t,
+                     const double *st, double *acc, double *accv)
+{
+    if constexpr (rhs_ncv<RHS>::value > 0) RHS::pgrad(col, s, x0, xn, p, pv, t, st, acc, accv);
+    else { (void)pv; (void)accv; RHS::pgrad(col, s, x0, xn, p, t, st, acc); }
+}
+// per-lane sums of an evaluation: EP_N columns, and CP_VMAX more (the vector entries' partials of the lane's column)
+// for a column-parameter form
+template <class RHS> using ColAcc = ThreadAccT<EP_N + (rhs_ncv<RHS>::value > 0 ? CP_VMAX : 0)>;
 
 // LDS reads that must stay single ds_read_b64 (2 LDS cycles per wave): merged pairs (ds_read2_b64)
 // take 8 cycles, half the bytes per clock, and the LDS pipe is what the rows / gather phases are
@@ -205,9 +231,9 @@ VA_HD void tile4_rfw_store(const Geo4 &g, const Tile4 &t, int D, const double (&
 // W_SCALAR: scalar RM and RF0, data at every row (the reference's Lorenz-96 example and every BASELINE
 // config): the weights factor out of the sums and the loops carry no weight registers.  WS = 0: weight arrays,
 // 1: W_SCALAR, 2: W_SCALAR with data at every merr_nskip-th row (rows without data masked by rg.has).
-template <class RHS, int DISC, int K, bool EDGE, int DC, int WS>
+template <class RHS, int DISC, int K, bool EDGE, int DC, int WS, class ACC>
 VA_HD void tile4_rows(const Dims &dm, const ProblemPtrs &pp, const Geo4 &g, const Tile4 &t,
-                      T4Regs<K, RHS::NE> &rg, ThreadAcc &acc)
+                      T4Regs<K, RHS::NE> &rg, ACC &acc)
 {
     constexpr bool W_SCALAR = WS != 0;                   // (WS == 2: scalar weights, data every nskip-th row -- rg.has)
     constexpr int HL = Halo<DISC>::HL, HR = Halo<DISC>::HR, NR = K + HL + HR, NQ = K + HL, NB = RHS::NB, NE = RHS::NE;
@@ -254,9 +280,9 @@ VA_HD void tile4_rows(const Dims &dm, const ProblemPtrs &pp, const Geo4 &g, cons
             xo[j] = ok ? xo[j] : 0.0;
 #pragma unroll
             for (int k = 0; k < NB; ++k) xn[k] = ok ? xn[k] : 0.0;
-            fo[j] = RHS::f(t.tx, xo[j], xn, t.p, tm[j], st);
+            fo[j] = col_f<RHS>(t.tx, xo[j], xn, t.p, t.pv, tm[j], st);
             fo[j] = ok ? fo[j] : 0.0;
-        } else fo[j] = RHS::f(t.tx, xo[j], xn, t.p, tm[j], st);
+        } else fo[j] = col_f<RHS>(t.tx, xo[j], xn, t.p, t.pv, tm[j], st);
         if (j >= HL && j < HL + K) {
 #pragma unroll
             for (int k = 0; k < NB; ++k) xnb[j - HL][k] = xn[k];
@@ -335,21 +361,26 @@ VA_HD void tile4_rows(const Dims &dm, const ProblemPtrs &pp, const Geo4 &g, cons
         double e[NE], diag;
         const int rowk = t.r0 + k < N ? t.r0 + k : N - 1;
         const double *stk = RHS::NSTIM > 0 ? pp.stim + (size_t)rowk * pp.nstim : nullptr;
-        RHS::scatter(t.tx, s, xo[j], xnb[k], t.p, tm[j], stk, e, diag);
+        col_scatter<RHS>(t.tx, s, xo[j], xnb[k], t.p, t.pv, tm[j], stk, e, diag);
         if (EDGE && RHS::GUARD_EDGE) {
             // a row that does not exist was evaluated at x = 0, where a right-hand side may be singular
             // (1/x, log x): its s = 0 does not make 0 * inf an exact zero, selects do
             const bool okk = t.r0 + k < N;
-            double pa[RHS::NP > 0 ? RHS::NP : 1];
+            constexpr int NCV = rhs_ncv<RHS>::value;
+            double pa[RHS::NP > 0 ? RHS::NP : 1], pav[NCV > 0 ? NCV : 1];
 #pragma unroll
             for (int u = 0; u < RHS::NP; ++u) pa[u] = 0.0;
-            RHS::pgrad(t.tx, s, xo[j], xnb[k], t.p, tm[j], stk, pa);
+#pragma unroll
+            for (int u = 0; u < NCV; ++u) pav[u] = 0.0;
+            col_pgrad<RHS>(t.tx, s, xo[j], xnb[k], t.p, t.pv, tm[j], stk, pa, pav);
 #pragma unroll
             for (int u = 0; u < RHS::NP; ++u) acc.v[EP_GP + u] += okk ? pa[u] : 0.0;
 #pragma unroll
+            for (int u = 0; u < NCV; ++u) acc.v[EP_N + u] += okk ? pav[u] : 0.0;
+#pragma unroll
             for (int u = 0; u < NE; ++u) e[u] = okk ? e[u] : 0.0;
             diag = okk ? diag : 0.0;
-        } else RHS::pgrad(t.tx, s, xo[j], xnb[k], t.p, tm[j], stk, acc.v + EP_GP);
+        } else col_pgrad<RHS>(t.tx, s, xo[j], xnb[k], t.p, t.pv, tm[j], stk, acc.v + EP_GP, acc.v + EP_N);
         rg.direct[k] = direct + diag; rg.xown[k] = xo[j];
 #pragma unroll
         for (int u = 0; u < NE; ++u) ep[u * g.EW1 + k * D] = e[u];
@@ -359,8 +390,8 @@ VA_HD void tile4_rows(const Dims &dm, const ProblemPtrs &pp, const Geo4 &g, cons
 // gather: gradient rows of the lane's run.  LSQ: also the sums the line search needs (g.d, g.g, max|g|).
 // The K gradient values of the lane's run come back in gvv[]; the caller stores them (rows >= N of an
 // edge tile hold exact zeros and must not be stored).
-template <class RHS, int DISC, int K, bool EDGE, int DC, int WS, bool LSQ>
-VA_HD void tile4_grad(const Dims &dm, const Geo4 &g, const Tile4 &t, const T4Regs<K, RHS::NE> &rg, ThreadAcc &acc,
+template <class RHS, int DISC, int K, bool EDGE, int DC, int WS, bool LSQ, class ACC>
+VA_HD void tile4_grad(const Dims &dm, const Geo4 &g, const Tile4 &t, const T4Regs<K, RHS::NE> &rg, ACC &acc,
                       double (&gvv)[K])
 {
     constexpr bool W_SCALAR = WS != 0;

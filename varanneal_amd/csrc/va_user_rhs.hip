@@ -18,6 +18,21 @@
 #endif
 #include VA_USER_RHS_HEADER
 
+namespace {
+// A model of more than RHS_BIG_NP parameters has no flat struct (RhsUser::FLAT = false): nothing of the flat kernel or of
+// k_seed is instantiated, and the host never asks for them (va_problem_create refuses such problems on any other kernel)
+template <class R> void user_launch_eval(const va::Dev &dv, hipStream_t s)
+{
+    if constexpr (va::rhs_flat<R>::value) va::launch_eval_rhs<R>(dv, s);
+    else { (void)dv; (void)s; }
+}
+template <class R> hipError_t user_prepare_eval(const va::Dev &dv)
+{
+    if constexpr (va::rhs_flat<R>::value) return va::prepare_eval_rhs<R>(dv);
+    else { (void)dv; return hipErrorNotSupported; }
+}
+}  // namespace
+
 extern "C" {
 
 // (NP, D, NSTIM, sizeof(Dev), sizeof(SeedState)) -- checked by va_rhs_load_module
@@ -29,13 +44,13 @@ void va_user_rhs_info(int *out)
 
 void va_user_launch_eval(const va::Dev *dv, void *stream)
 {
-    va::launch_eval_rhs<va::RhsUser>(*dv, (hipStream_t)stream);
+    user_launch_eval<va::RhsUser>(*dv, (hipStream_t)stream);
 }
 
 // once per problem handle, on the handle's device: opt the kernel in to the LDS it needs
 int va_user_prepare_eval(const va::Dev *dv)
 {
-    return (int)va::prepare_eval_rhs<va::RhsUser>(*dv);
+    return (int)user_prepare_eval<va::RhsUser>(*dv);
 }
 
 // the persistent per-seed ladder kernel (va_persist.h) for this model: few seeds, short paths
@@ -50,10 +65,18 @@ int va_user_seed_kernel(const va::Dev *dv, int launch, void *stream)
 //           system) on the wave-private kernel k_eval4; W = 1 for scalar weights
 //   EK = 5: a stencil's column form on the streaming kernel k_eval5 (wide even states, autonomous)
 //   EK = 3: a stencil's ghosted form (struct RhsUserG) on the workgroup kernel k_eval3; W = threads per workgroup
-// (eval kernel or 0, DISC, K, W, products per element [4, 5], ghost columns [3], reaches xl, xr, gl, gr [5], -, dense linear part)
-#if defined(VA_USER_EK) && VA_USER_EK == 5 && defined(VA_USER_COL)
+// A model in column-parameter form (struct RhsUserColP: a stencil with per-column parameter vectors) takes the place of
+// the column form for EK = 4 and 5.
+// (eval kernel or 0, DISC, K, W, products per element [4, 5], ghost columns [3], reaches xl, xr, gl, gr [5], dense linear
+// part, vectors of the column-parameter form)
+#if defined(VA_USER_COLP)
+#define VA_USER_COLT va::RhsUserColP
+#elif defined(VA_USER_COL)
+#define VA_USER_COLT va::RhsUserCol
+#endif
+#if defined(VA_USER_EK) && VA_USER_EK == 5 && defined(VA_USER_COLT)
 #define VA_USER_VARIANT 5
-#elif defined(VA_USER_EK) && VA_USER_EK == 4 && defined(VA_USER_COL)
+#elif defined(VA_USER_EK) && VA_USER_EK == 4 && defined(VA_USER_COLT)
 #define VA_USER_VARIANT 4
 #elif defined(VA_USER_EK) && VA_USER_EK == 3 && defined(VA_USER_GHOST)
 #define VA_USER_VARIANT 3
@@ -65,11 +88,13 @@ void va_user_variant_info(int *out)
 #ifdef VA_USER_VARIANT
     out[0] = VA_USER_VARIANT; out[1] = VA_USER_DISC; out[2] = VA_USER_K; out[3] = VA_USER_W;
 #if VA_USER_VARIANT == 5
-    out[4] = va::RhsUserCol::NE;
-    out[6] = va::t5_xl<va::RhsUserCol>(); out[7] = va::t5_xr<va::RhsUserCol>();
-    out[8] = va::t5_gl<va::RhsUserCol>(); out[9] = va::t5_gr<va::RhsUserCol>();
+    out[4] = VA_USER_COLT::NE;
+    out[6] = va::t5_xl<VA_USER_COLT>(); out[7] = va::t5_xr<VA_USER_COLT>();
+    out[8] = va::t5_gl<VA_USER_COLT>(); out[9] = va::t5_gr<VA_USER_COLT>();
+    out[11] = va::rhs_ncv<VA_USER_COLT>::value;
 #elif VA_USER_VARIANT == 4
-    out[4] = va::RhsUserCol::NE;
+    out[4] = VA_USER_COLT::NE;
+    out[11] = va::rhs_ncv<VA_USER_COLT>::value;
 #else
     out[5] = va::RhsUserG::GHOST;
 #endif
@@ -78,20 +103,20 @@ void va_user_variant_info(int *out)
 #if defined(VA_USER_VARIANT) && VA_USER_VARIANT == 5
 void va_user_launch_variant(const va::Dev *dv, void *stream)
 {
-    (void)va::eval5_run<va::RhsUserCol, VA_USER_DISC, va::RhsUserCol::D>(*dv, false, (hipStream_t)stream);
+    (void)va::eval5_run<VA_USER_COLT, VA_USER_DISC, VA_USER_COLT::D>(*dv, false, (hipStream_t)stream);
 }
 int va_user_prepare_variant(const va::Dev *dv)
 {
-    return (int)va::eval5_run<va::RhsUserCol, VA_USER_DISC, va::RhsUserCol::D>(*dv, true, nullptr);
+    return (int)va::eval5_run<VA_USER_COLT, VA_USER_DISC, VA_USER_COLT::D>(*dv, true, nullptr);
 }
 #elif defined(VA_USER_VARIANT) && VA_USER_VARIANT == 4
 void va_user_launch_variant(const va::Dev *dv, void *stream)
 {
-    va::launch_eval4_one<va::RhsUserCol, VA_USER_DISC, VA_USER_K, va::RhsUserCol::D, VA_USER_W != 0>(*dv, (hipStream_t)stream);
+    va::launch_eval4_one<VA_USER_COLT, VA_USER_DISC, VA_USER_K, VA_USER_COLT::D, VA_USER_W != 0>(*dv, (hipStream_t)stream);
 }
 int va_user_prepare_variant(const va::Dev *dv)
 {
-    return (int)va::prepare_eval4_one<va::RhsUserCol, VA_USER_DISC, VA_USER_K, va::RhsUserCol::D, VA_USER_W != 0>(*dv);
+    return (int)va::prepare_eval4_one<VA_USER_COLT, VA_USER_DISC, VA_USER_K, VA_USER_COLT::D, VA_USER_W != 0>(*dv);
 }
 #elif defined(VA_USER_VARIANT)
 void va_user_launch_variant(const va::Dev *dv, void *stream)
@@ -101,6 +126,17 @@ void va_user_launch_variant(const va::Dev *dv, void *stream)
 int va_user_prepare_variant(const va::Dev *dv)
 {
     return (int)va::prepare_eval3_one<va::RhsUserG, VA_USER_DISC, VA_USER_K, va::RhsUserG::D, VA_USER_W>(*dv);
+}
+#endif
+
+#if defined(VA_USER_COLP)
+// the column-parameter form's map: (shared scalars S, vectors V), then the global parameter index of each shared scalar
+// and of each vector entry (v, column i) at S + v D + i
+void va_user_colp_map(int *out)
+{
+    out[0] = va::RhsUserColP::NP; out[1] = va::RhsUserColP::NCV;
+    for (int k = 0; k < va::RhsUserColP::NP; ++k) out[2 + k] = va::va_colp_sidx[k];
+    for (int e = 0; e < va::RhsUserColP::NCV * va::RhsUserColP::D; ++e) out[2 + va::RhsUserColP::NP + e] = va::va_colp_vidx[e];
 }
 #endif
 

@@ -247,11 +247,17 @@ class Annealer(HIPmin):
         stim = None
         if self.stim is not None:
             stim = np.asarray(self.stim, dtype=np.float64)
+        colparams = None
         if self._rhs_name is not None and stim is None:
             impl, NPr, _ = _rhs.REGISTRY[self._rhs_name]
-            if self.NP != NPr:
+            if self.NP == NPr:
+                rhs_id = self._rhs_name
+            elif callable(self.f):
+                # the built-in model called with a parameter vector (e.g. Lorenz-96 with a forcing per site): only the
+                # built-in kernels need exactly NPr parameters -- the callable is generated, in column-parameter form
+                rhs_id, colparams = None, True
+            else:
                 raise ValueError("RHS %r takes %d parameter(s), P0 has %d" % (self._rhs_name, NPr, self.NP))
-            rhs_id = self._rhs_name
         else:
             rhs_id = None                             # any other callable: a generated module, built below
                                                       # once the weights and bounds (its kernel variant) are known
@@ -358,7 +364,7 @@ class Annealer(HIPmin):
                                         bounded=self._device_bounds, p_time_dependent=self._tdp,
                                         reach=reach, Lidx=self.Lidx)
             mod = codegen.module_for(self.f, self.D, self.NP, nstim, 1 if stim is None else stim.ndim,
-                                     p_rows=self._tdp, col_variant=variant)
+                                     p_rows=self._tdp, col_variant=variant, colparams=colparams)
             rhs_id = _capi.load_rhs_module(mod["so"])
             self._rhs_module = mod
 
