@@ -1,7 +1,8 @@
 // tile5_check.cpp -- CPU check of the streaming kernel's index arithmetic (csrc/va_tile5.h, va_eval5.h): for a state
 // width D and column-form reaches, walk every strip and every lane exactly as k_eval5 computes them -- the staged
 // image's source columns, the lane's own column and its stencil neighbours inside a staged row, the product-array
-// slots of the gather, the packed store lanes -- and verify them against the plain definition (cyclic columns).
+// slots of the gather, the packed store lanes, the column-parameter tail's walk over the tiles -- and verify them
+// against the plain definition (cyclic columns).
 // Test infrastructure (tests/test_tile5_geometry.py); prints "OK <D> ..." or the first mismatch.
 #include <cstdio>
 #include <cstdlib>
@@ -75,7 +76,39 @@ int main(int argc, char **argv)
             if (2 * hp > 64) rc = fail("store lanes", D, s, 0, 2 * hp, 64);
         }
         if (!rc && covered != D) rc = fail("coverage", D, g.NS, 0, covered, D);
-        if (!rc) std::printf("OK %d NS=%d CW=%d PR=%d NACT=%d WPG=%d NSG=%d\n", D, g.NS, g.CW, g.PR, g.NACT, g.WPG, g.NSG);
+        // the column-parameter tail (va_epilogue.h colp_tail) adds column c's partials over the tiles t0, t0 + NSG, ...
+        // of a launch of NSEG * NSG tiles, t0 = the group of c's strip: exactly the tiles whose strips own c, each once,
+        // where k_eval5 maps tile -> (segment sg = tile / NSG, group grp = tile % NSG) -> strip grp * WPG + wave
+        int walked = 0;
+        for (int nseg = 1; nseg <= 5 && !rc; ++nseg) {
+            const int ntiles = nseg * g.NSG;
+            for (int c = 0; c < D && !rc; ++c) {
+                const int s5 = tile5_strip_of(D, g.NS, c);
+                if (tile5_c0(D, g.NS, s5) > c || tile5_c0(D, g.NS, s5 + 1) <= c) rc = fail("strip of column", D, s5, c, tile5_c0(D, g.NS, s5), c);
+                std::vector<int> read(ntiles, 0), owns(ntiles, 0);
+                int t0 = -1, ts = 0;
+                tile5_col_tiles(g, c, t0, ts);
+                if (t0 < 0 || ts < 1) { rc = fail("tail walk start / stride", D, s5, c, t0, ts); break; }
+                for (int t = t0; t < ntiles; t += ts) read[t]++;
+                for (int tile = 0; tile < ntiles; ++tile) {
+                    const int sg = tile / g.NSG, grp = tile - sg * g.NSG;
+                    if (sg >= nseg) rc = fail("tile segment", D, grp, tile, sg, nseg);
+                    for (int wave = 0; wave < g.WPG; ++wave) {
+                        const int strip = grp * g.WPG + wave;
+                        if (strip < g.NS && tile5_c0(D, g.NS, strip) <= c && c < tile5_c0(D, g.NS, strip + 1)) owns[tile]++;
+                    }
+                }
+                int nread = 0;
+                for (int tile = 0; tile < ntiles && !rc; ++tile) {
+                    if (read[tile] > 1 || owns[tile] > 1) rc = fail("tile read twice / column owned twice", D, s5, tile, read[tile], owns[tile]);
+                    else if (read[tile] != owns[tile]) rc = fail("tail tile walk", D, s5, tile, read[tile], owns[tile]);
+                    nread += read[tile];
+                }
+                if (!rc && nread != nseg) rc = fail("tiles per column", D, s5, c, nread, nseg);
+                ++walked;
+            }
+        }
+        if (!rc) std::printf("OK %d NS=%d CW=%d PR=%d NACT=%d WPG=%d NSG=%d WALK=%d\n", D, g.NS, g.CW, g.PR, g.NACT, g.WPG, g.NSG, walked);
     }
     return rc;
 }

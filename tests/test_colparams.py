@@ -161,3 +161,27 @@ def test_builtin_model_with_a_parameter_vector_goes_to_codegen(monkeypatch):
     b.anneal(rng.randn(N, D), np.array([8.0]), 2.0, [0], 4.0, 1e-2, list(range(0, D, 2)), [0], disc="trapezoid",
              verbose=False)
     assert calls == [] and _Recorder.made[-1].kw["rhs"] == "lorenz96"
+
+
+def test_recognised_at_the_limits():
+    """24 shared scalars (RHS_MAX_NP: the 32-column partial sums) and 4 vectors (CP_VMAX), interleaved, are recognised;
+    one more scalar or one more vector is not -- and each of those models has the form bar the cap"""
+    from _util import colparam_model
+    D = 20
+    cp = _form(colparam_model(24, 4, interleaved=True), D, 24 + 4 * D)
+    assert cp is not None and cp["S"] == 24 and cp["V"] == 4 and list(cp["sidx"]) == list(range(24))
+    assert cp["vidx"][:, :2].tolist() == [[24, 28], [25, 29], [26, 30], [27, 31]]
+    for S, V in ((25, 1), (0, 5)):
+        NP = S + V * D
+        assert _form(colparam_model(S, V), D, NP) is None, (S, V)
+        exprs, syms = codegen.trace(colparam_model(S, V), D, NP)
+        cp = codegen.colparam_form(exprs, syms, D, NP, max_ncv=5, max_shared=25)
+        assert cp is not None and (cp["S"], cp["V"]) == (S, V)
+
+
+@pytest.mark.parametrize("S,V", [(25, 1), (0, 5)])
+def test_past_the_limits_and_the_cap_is_refused(S, V):
+    """D = 200: 225 / 1000 parameters, past the flat kernel's 128, one scalar / one vector more than the form takes"""
+    from _util import colparam_model
+    with pytest.raises(NotImplementedError, match="more than 128 parameters"):
+        codegen.module_for(colparam_model(S, V), 200, S + V * 200, compile=False)

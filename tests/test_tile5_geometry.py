@@ -1,6 +1,6 @@
 """CPU: index arithmetic of the streaming evaluation kernel k_eval5 (csrc/va_tile5.h) -- strips, staged images with
-cyclic ghost columns, stencil neighbours, gather senders, packed store lanes -- checked for every even state width
-from 66 to 1024 by a g++ build of tests/cpu_emul/tile5_check.cpp (the same header the kernel includes)."""
+cyclic ghost columns, stencil neighbours, gather senders, packed store lanes, the column-parameter tail's tile walk --
+checked for every even state width from 66 to 1024 by a g++ build of tests/cpu_emul/tile5_check.cpp (the same header the kernel includes)."""
 import os
 import subprocess
 
@@ -18,6 +18,10 @@ def test_every_even_width(tmp_path):
     assert len(lines) == len(widths) and all(ln.startswith("OK ") for ln in lines), [ln for ln in lines if not ln.startswith("OK ")][:5]
     c4 = [ln for ln in lines if ln.startswith("OK 200 ")][0]
     assert "NS=4" in c4 and "CW=56" in c4 and "PR=32" in c4 and "WPG=4 NSG=1" in c4      # BASELINE config 4: 48 + 48 + 48 + 56 columns
+    # the column-parameter tail's tile walk ran for every column at 1..5 segments; past 224 columns over several groups
+    for d, nsg in ((200, 1), (226, 2), (250, 2), (450, 3), (1000, 5)):
+        ln = [ln for ln in lines if ln.startswith("OK %d " % d)][0]
+        assert ("NSG=%d " % nsg) in ln and ln.endswith(" WALK=%d" % (5 * d)), ln
 
 
 def test_narrow_and_odd_widths_are_refused(tmp_path):

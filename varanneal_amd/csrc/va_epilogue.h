@@ -135,12 +135,7 @@ __device__ __forceinline__ void colp_tail(const Dev &dv, int b, int lane, double
         const int k = e < VD ? dv.cpmap[NT + S + e] : -1;
         if (k < 0) continue;
         int t0 = 0, ts = 1;
-        if (dv.cpnsg > 0) {
-            const int c = e % D;
-            int s5 = 0;
-            while (s5 + 1 < dv.g5.NS && tile5_c0(D, dv.g5.NS, s5 + 1) <= c) ++s5;
-            t0 = s5 / dv.g5.WPG; ts = dv.cpnsg;
-        }
+        if (dv.cpnsg > 0) tile5_col_tiles(dv.g5, e % D, t0, ts);
         const double g = col_reduce<true>(tb + e, dm.ntiles, VD, t0, ts, false);
         gt[dm.ND + k] = g;
         if (use_d) gtd = fma(g, d[dm.ND + k], gtd);

@@ -75,6 +75,13 @@ VA_HD constexpr int tile5_c0(int D, int NS, int s5)
 {
     return s5 >= NS ? D : 8 * ((s5 * (D / 8)) / NS);
 }
+// the strip that owns column c (0 <= c < D)
+VA_HD constexpr int tile5_strip_of(int D, int NS, int c)
+{
+    int s5 = 0;
+    while (s5 + 1 < NS && tile5_c0(D, NS, s5 + 1) <= c) ++s5;
+    return s5;
+}
 VA_HD constexpr int tile5_maxw(int D, int NS)
 {
     int m = 0;
@@ -114,6 +121,14 @@ VA_HD constexpr bool tile5_ok(int D, int xl, int xr, int gl, int gr)
     if (D <= 64 || (D & 1)) return false;
     const Geo5 g = tile5_cols(D, xl, xr, gl, gr);
     return g.PR <= 32 && g.NACT <= 64 && g.NS <= T5_MAX_STRIPS && 2 * g.PR <= D;
+}
+
+// the tiles of a k_eval5 launch (tile = segment * NSG + group, strip = group * WPG + wave) whose strips own column c:
+// t0, t0 + ts, ... below NSEG * NSG -- the column's group in every segment (the column-parameter tail's walk)
+VA_HD void tile5_col_tiles(const Geo5 &g, int c, int &t0, int &ts)
+{
+    t0 = tile5_strip_of(g.D, g.NS, c) / g.WPG;
+    ts = g.NSG;
 }
 
 VA_HD constexpr int t5_wrap(int c, int D) { return c < 0 ? c + D : (c >= D ? c - D : c); }
