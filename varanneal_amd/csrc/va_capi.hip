@@ -19,6 +19,7 @@
 
 #include "../../include/varanneal_amd.h"
 #include "va_device.h"
+#include "va_eval_geo.h"
 #include "va_nnet.h"
 #include "va_eval_flat.h"
 #include "va_persist.h"
@@ -50,9 +51,7 @@ int fail(int code, const char *fmt, ...)
 
 // generated right-hand-side modules (va_rhs_load_module); ids are VA_RHS_USER_BASE + index
 struct UserRhs {
-    // the ONE column-run instantiation the module carries besides its flat kernel, if any (va_user_rhs.hip):
-    // (eval kernel 0 / 3 / 4 / 5, DISC, K, W_SCALAR [4] or threads [3], NE [4, 5], GHOST [3])
-    int var[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // (+ the column form's reaches xl, xr, gl, gr [5]; [10]: the flat kernel carries a dense linear part)
+    ModuleVariant variant;     // the ONE column-run instantiation the module carries besides its flat kernel, if any (va_user_rhs.hip)
     void (*launch_var)(const Dev *, void *) = nullptr;
     int (*prepare_var)(const Dev *) = nullptr;
     std::string path;
@@ -61,7 +60,7 @@ struct UserRhs {
     int (*prepare)(const Dev *) = nullptr;
     int (*seed_kernel)(const Dev *, int, void *) = nullptr;      // the persistent per-seed ladder kernel (va_persist.h), if the module carries it
     int NP = 0, D = 0, NSTIM = 0;
-    // [11] > 0: the column-run instantiation is of the model's column-parameter form (RhsUserColP); its map
+    // variant.n_colp_vectors > 0: the column-run instantiation is of the model's column-parameter form (RhsUserColP); its map
     // (va_user_colp_map): shared scalars S, vectors V, then the global index of each shared scalar and of each vector entry
     std::vector<int> colp;
 };
@@ -143,240 +142,6 @@ void run_eval(va_handle h, int epi)
     if (h->is_nnet) { launch_nnet_eval(h->dv, h->nn, h->stream, h->user_act); return; }   // (small nets: k_nnet_small carries the tail)
     if (h->user_launch) h->user_launch(&h->dv, (void *)h->stream);
     else launch_eval(h->dv, h->rhs, h->stream);
-}
-
-// Tile geometry of the eval kernel: which mapping, rows per workgroup, threads.
-// ne: products per element of the model's column form (RhsL96s::NE for the built-in; a generated
-// module's RhsUserCol::NE), or 0 when the model has none; ghost: ghost columns per side of its ghosted
-// form for the workgroup column-run kernel (RhsL96g::GHOST; a module's RhsUserG::GHOST), or 0.  A model
-// with neither runs the flat kernel.
-// reach5: {xl, xr, gl, gr} of a column form that the streaming kernel (emode 5, va_tile5.h) may run, or NULL.
-void pick_eval_geometry(const va_problem_desc *d, Dims &dm, Geo4 &g4, int ne, int ghost,
-                        const int *reach5 = nullptr, Geo5 *g5 = nullptr, std::vector<int> *ystrip = nullptr)
-{
-    bool user_rhs = ne <= 0 && ghost <= 0;
-    dm.ghost = ghost > 0 ? ghost : 2;
-    user_rhs = user_rhs || d->p_time_dependent || d->rm_kind == 2 || d->rf_kind == 2;   // per-row parameters / full RM or RF matrices: flat kernel only
-    user_rhs = user_rhs || (d->lower && d->upper);                   // box bounds: the flat kernel carries the clamp / projected gradient
-    const int D = d->D, N = d->N_model;
-    const bool sh = d->disc == VA_DISC_SIMPSON_HERMITE;
-    const int HLR = sh ? 3 : 2;
-    dm.emode = d->eval_kernel;
-    // auto: wave-private column runs for narrow states that fill a wave, workgroup column runs up
-    // to 1024 columns, flat mapping beyond
-    if (dm.emode == 2) dm.emode = 3;                      // (the row-strided kernel of round 1 is gone)
-    // streaming column strips: wide even states, a column form, scalar or per-row weights with
-    // data at every model time (what every BASELINE config has); anything else keeps the tile kernels
-    const bool ws5 = d->rm_kind <= 1 && d->rf_kind <= 1 && d->merr_nskip >= 1 && d->L >= 1;     // (full matrices: flat kernel)
-    const bool can5 = reach5 && g5 && ystrip && !user_rhs && ne > 0 && ws5 && D > 64 && (!sh || (N & 1)) &&
-                      tile5_ok(D, reach5[0], reach5[1], reach5[2], reach5[3]);
-    if (dm.emode == 5 && !can5) dm.emode = 0;
-    if (dm.emode < 1 || dm.emode > 5) dm.emode = (tile4_ok(D) && ne > 0) ? 4 : (can5 ? 5 : ((D <= 1024 && ghost > 0) ? 3 : 1));
-    if (user_rhs) dm.emode = 1;                           // no column form (or a case only the flat kernel carries)
-    if (dm.emode == 5) {
-        Geo5 g = tile5_cols(D, reach5[0], reach5[1], reach5[2], reach5[3]);
-        g.ne = ne;
-        // segments: as many workgroups as the chip holds at once (four 4-wave groups per CU: 128 registers, 40 KiB
-        // of LDS each), every one with the same number of rows; at least 32 rows per segment
-        const long per_row = (long)d->batch * g.NSG;
-        long nseg = (4L * 256) / per_row;
-        if (d->tile_rows > 0) nseg = (N + d->tile_rows - 1) / d->tile_rows;
-        if (nseg > N / 32) nseg = N / 32;
-        if (nseg < 1) nseg = 1;
-        g.SEGL = (int)((N + nseg - 1) / nseg);
-        g.SEGL = (g.SEGL + 1) & ~1;
-        g.NSEG = (N + g.SEGL - 1) / g.SEGL;
-        // observation rows per strip: the data columns of the strip's own state columns (Lidx ascending on the device)
-        std::vector<int> ls(d->Lidx, d->Lidx + d->L);
-        std::sort(ls.begin(), ls.end());
-        ystrip->assign(2 * g.NS, 0);
-        g.YPMAX = 1;
-        for (int s5 = 0; s5 < g.NS; ++s5) {
-            const int c0 = tile5_c0(D, g.NS, s5), c1 = tile5_c0(D, g.NS, s5 + 1);
-            const int l0 = (int)(std::lower_bound(ls.begin(), ls.end(), c0) - ls.begin());
-            const int l1 = (int)(std::lower_bound(ls.begin(), ls.end(), c1) - ls.begin());
-            int start = l0 & ~1;
-            int yp = (l1 - start + 1) / 2;
-            if (yp < 1) yp = 1;                           // (every staging instruction has an active lane: the queue counts are exact)
-            (*ystrip)[2 * s5] = start; (*ystrip)[2 * s5 + 1] = yp;
-            if (yp > g.YPMAX) g.YPMAX = yp;
-        }
-        // ring depth: four slots (three requested ahead) while four workgroups still share a CU's 160 KiB, else three.
-        // Measured at C4 (profiles/r03_e5_experiments.txt): 3 and 4 slots equal; 6 slots drop a workgroup per CU (+33 %)
-        g.xdpp = (reach5[2] <= 2 && reach5[3] <= 2) ? 1 : 0;
-        auto fits = [&](int nslot, bool lsr) { return (size_t)g.WPG * tile5_wave_doubles(g, nslot, lsr) * sizeof(double) <= 40 * 1024; };
-        g.nslot = fits(4, false) ? 4 : 3;
-        g.nslot_ls = fits(4, true) ? 4 : 3;
-        g.warr = (d->rm_kind == 1 || d->rf_kind == 1 || d->merr_nskip > 1) ? 1 : 0;
-        if (g.warr) g.nslot = g.nslot_ls = 3;          // (two more images per slot; only the three-slot instantiations exist)
-        g.LY = (d->L + 1) & ~1;                        // (data rows are staged by 16-byte pieces: an odd L gets a pad column on the device)
-        if (g.YPMAX <= 32) {
-            *g5 = g;
-            dm.RY = 0; dm.NT = 64 * g.WPG; dm.maxr = 2; dm.T = g.SEGL;
-            dm.ntiles = g.NSEG * g.NSG;
-            return;
-        }
-        dm.emode = (D <= 1024 && ghost > 0) ? 3 : 1;
-    }
-    if (dm.emode == 4 && (!tile4_ok(D) || ne <= 0)) dm.emode = 3;
-    if (dm.emode == 3 && ghost <= 0) dm.emode = 1;
-    if (dm.emode == 3 && D > 1024) dm.emode = 1;          // column runs: a lane per column
-    int tmin, tmax;
-    if (dm.emode == 4) {
-        // wave-private column runs: T = 4 waves x RW runs x K rows.  K is the run length that gives
-        // every CU the same number of workgroups when the grid is only a few per CU (C3: 64 seeds,
-        // N = 1000: K = 7 -> 12 tiles x 64 = 768 = 3 x 256), 6 otherwise
-        const int RW = 64 / D, rows1 = 4 * RW;
-        int K = 6;
-        auto ntl = [&](int k) { return (long)d->batch * ((N + rows1 * k - 1) / (rows1 * k)); };
-        if (ntl(K) < 256) K = 4;
-        else if (ntl(K) >= 8 * 256) {
-            // many rounds of workgroups: the run length that stages the fewest rows (own + halo) per seed,
-            // longest on ties, up to 7 (8 drops the kernel to two waves per SIMD).  N = 1000, D = 20: K = 7
-            // (12 tiles x 9 rows per lane against 14 x 8 for K = 6): 370 vs 409 us at 4096 seeds
-            long best = -1;
-            for (int k = 5; k <= 7; ++k) {
-                if (sh && (k & 1)) continue;
-                const long cost = (long)((N + rows1 * k - 1) / (rows1 * k)) * (k + (sh ? 3 : 2));
-                if (best < 0 || cost <= best) { best = cost; K = k; }
-            }
-        } else {
-            // a few workgroups per CU, all resident at once: the busiest CU sets the time.  Pick the K whose (workgroups per
-            // CU, rounded up) x (rows per lane + fixed per-workgroup cost) is smallest, e.g. C3 (64 seeds, N = 1000):
-            // K = 7 gives 12 tiles x 64 = 768 workgroups = exactly 3 per CU.  Simpson-Hermite (even K; 8 runs at two waves
-            // per SIMD, so only two workgroups per CU are resident): rounds of resident workgroups x rows per lane --
-            // N = 1001: K = 4 -> 2 rounds x 6 rows (11.4 us) against 2 x 8 at K = 6 (11.7) and 2 x 10 at K = 8 (12.1)
-            long best = -1;
-            for (int k = sh ? 4 : 5; k <= 8; ++k) {
-                if (sh && (k & 1)) continue;              // Simpson-Hermite runs start on even rows
-                const long per_round = sh ? 256L * (k <= 7 ? 3 : 2) : 256L;
-                const long cost = ((ntl(k) + per_round - 1) / per_round) * (k + 2) * 4 + (k == 6 ? 0 : 1);     // ties go to 6
-                if (best < 0 || cost < best) { best = cost; K = k; }
-            }
-            // Simpson-Hermite, D = 20, scalar weights: runs of 12 rows (two workgroups per CU, no spill) when they put the whole
-            // grid in ONE round of resident workgroups -- a launch of this size is a chain of latencies, not of rows: N = 1001,
-            // 64 seeds: K = 4 -> 21 tiles, 1.75 rounds, 11.3 us; K = 12 -> 7 tiles, 448 workgroups, 9.4 us (trapezoid at K = 7: 8.6)
-            // (measured for the built-in right-hand side: a generated model keeps the chooser's K unless asked)
-            if (sh && D == 20 && d->rhs == VA_RHS_LORENZ96 && d->rm_kind == 0 && d->rf_kind == 0 && ntl(12) <= 2 * 256 && ntl(K) > 3 * 256) K = 12;
-        }
-        if (d->tile_rows > 0) {
-            K = (d->tile_rows + rows1 - 1) / rows1;
-            const bool k12 = D == 20 && d->rm_kind == 0 && d->rf_kind == 0 && (d->merr_nskip == 1 || d->rhs == VA_RHS_LORENZ96);     // (the one longer run compiled)
-            K = K < 4 ? 4 : (K >= 12 && k12 ? 12 : (K > 8 ? 8 : K));
-            if (sh && (K & 1)) ++K;
-        }
-        // weight arrays / data every nskip-th row: runs of 6 and 7 rows do not fit three waves per SIMD's 168 registers
-        // with their weight registers (35-58 spilled; measured at the C3 shape, profiles/r03_f3_variants.txt: 21 us
-        // against 13 us for K = 5): those problems run K <= 5, or 8 at two waves per SIMD -- except the built-in
-        // right-hand side at D = 20, whose instantiations park the RF weights in LDS, fold the RM weights into the data
-        // registers before the f evaluations (va_tile4.h) and mask merr_nskip's rows by a bit each
-        {
-            const bool ws4 = (d->rm_kind == 0 && d->rf_kind == 0 && d->merr_nskip == 1) || (D == 20 && d->rhs == VA_RHS_LORENZ96);
-            if (!ws4 && (K == 6 || K == 7)) K = sh ? 4 : 5;
-        }
-        // column forms with many products per element (a ring of coupled units: 8): the product arrays grow with the run
-        // length; keep at least two workgroups per CU (measured, five 4-state units at the C3 shape: K = 4 23.4 us, K = 7 31.5)
-        if (d->tile_rows <= 0) {
-            while (K > 4) {
-                const Geo4 gt = sh ? tile4_geo<3>(D, K, ne, 1) : tile4_geo<2>(D, K, ne, 1);
-                if (sizeof(double) * (size_t)gt.NW * gt.WAVE <= 80 * 1024) break;
-                K -= (sh || K == 5) ? (K == 5 ? 1 : 2) : 1;
-            }
-        }
-        // (one wave per SIMD walking SUB sub-tiles in turn was measured slower than co-resident waves -- DESIGN.md section 7;
-        // only SUB = 1 is instantiated, and the host never asks for anything else)
-        const int SUB = 1;
-        g4 = sh ? tile4_geo<3>(D, K, ne, SUB) : tile4_geo<2>(D, K, ne, SUB);
-        // (D = 20 is compiled with its geometry constant: the kernel sizes its staging loop exactly)
-        if ((D == 20 || (g4.XP + 63) / 64 <= T4_NI_MAX) && tile4_magic_ok(g4)) {
-            dm.RY = 4 * RW; dm.NT = 256; dm.maxr = K; dm.T = g4.T;
-            dm.ntiles = (N + dm.T - 1) / dm.T;
-            return;
-        }
-        dm.emode = ghost > 0 ? 3 : 1;
-    }
-    if (dm.emode == 3) {
-        // column-run kernel: T = RY*K exactly, K rows per lane in {4, 6, 8}
-        dm.RY = tile3_RY(D); dm.NT = tile3_threads(D);
-        // K = 6 keeps the kernel at 128 VGPRs (4 waves/SIMD) and measured best from 64 to 4096
-        // seeds (profiles/r01_sweep_*.txt); drop to 4 when that leaves CUs without a workgroup
-        int K = 6;
-        if ((long)d->batch * ((N + dm.RY * K - 1) / (dm.RY * K)) < 256) K = 4;
-        else if ((long)d->batch * ((N + dm.RY * K - 1) / (dm.RY * K)) < 8 * 256 && dm.NT == 256) {
-            // small grids run as a handful of workgroups per CU, all resident at once: the busiest
-            // CU sets the time.  Pick the K whose (workgroups per CU, rounded up) x (rows per lane +
-            // fixed per-workgroup cost) is smallest, e.g. C3 (64 seeds, N = 1000): K = 7 gives
-            // 12 tiles x 64 = 768 workgroups = exactly 3 per CU (10.2 us) against 3.5 for K = 6 (10.7 us).
-            long best = -1;
-            for (int k = 5; k <= 8; ++k) {
-                if (sh && (k & 1)) continue;              // Simpson-Hermite runs start on even rows
-                const long wgs = (long)d->batch * ((N + dm.RY * k - 1) / (dm.RY * k));
-                const long cost = ((wgs + 255) / 256) * (k + 2) * 4 + (k == 6 ? 0 : 1);     // ties go to 6
-                if (best < 0 || cost < best) { best = cost; K = k; }
-            }
-        }
-        if (d->tile_rows > 0) {
-            K = (d->tile_rows + dm.RY - 1) / dm.RY;
-            K = K < 4 ? 4 : (K > 8 ? 8 : K);
-            if (sh && (K & 1)) ++K;
-        }
-        if (D > 64 && d->tile_rows <= 0 && (long)d->batch * ((N + dm.RY * 8 - 1) / (dm.RY * 8)) >= 256)
-            K = 8;                                         // few lanes per column: long runs keep the halo share down
-        if (dm.NT == 1024 && K > 6) K = 6;                 // (1024-thread groups live on 128 registers: runs of 8 rows spill 20-88 of them)
-        for (;;) {                                        // shrink until the staging arrays fit in LDS
-            const size_t elems = (size_t)tile3_stage_elems(K, D, dm.ghost, dm.RY, HLR) + tile3_s_elems(K, D, dm.ghost, dm.RY);
-            if (sizeof(double) * elems <= (D <= 64 ? 60 : (D <= 512 ? 78 : 150)) * 1024 || K <= 4) break;   // two groups per CU (one beyond D = 512)
-            K -= (sh || K == 5) ? (K == 5 ? 1 : 2) : 1;  // Simpson-Hermite keeps K even; never below 4
-        }
-        dm.maxr = K; dm.T = dm.RY * K;
-        dm.ntiles = (N + dm.T - 1) / dm.T;
-        return;
-    }
-    if (dm.emode == 2) {
-        dm.RY = tile2_RY(D); dm.NT = tile2_threads(D);
-        const int narr = sh ? 3 : 2;
-        const int lds_rows = (int)((60 * 1024) / (narr * sizeof(double) * D));
-        // 8 rows per lane keeps the register tile small; go to 16 when that would leave
-        // tiles so short that the halo rows dominate (large D)
-        dm.maxr = (8 * dm.RY - HLR >= 24) ? 8 : 16;
-        int rmax = dm.maxr * dm.RY;
-        if (rmax > lds_rows) rmax = lds_rows;
-        tmax = rmax - HLR;
-        tmin = dm.RY;
-    } else {
-        dm.RY = 0; dm.NT = EVAL_THREADS; dm.maxr = 0;
-        // LDS: 3 staged arrays of (T+halo) rows (4 when the right-hand side has a dense linear part: J^T s of it)
-        // ~24 KiB per workgroup (six per CU) measured best (D = 100: T = 8, 349 us against 403 us at
-        // T = 18); wider states take 48 KiB, then whatever still gives two owned rows
-        const size_t narr = 3 + (dm.lin ? 1 : 0);
-        auto rows_in = [&](size_t kib) { return (int)((kib * 1024) / (narr * sizeof(double) * D)) - HLR; };
-        tmax = rows_in(24);
-        if (dm.lin) {
-            // the matrix cores take 16 staged rows at a time and every workgroup reads the whole table of the linear
-            // part per product: the smallest budget that stages >= 16 rows, up to 80 KiB (two workgroups per CU)
-            for (size_t kib : {24, 48, 80}) { tmax = rows_in(kib); if (tmax + HLR >= 16) break; }
-        }
-        if (tmax < 2) tmax = rows_in(48);
-        if (tmax < 2) tmax = rows_in(150);
-        if (dm.lin && d->tile_rows > tmax && d->tile_rows <= rows_in(150)) tmax = d->tile_rows;     // (an explicit run length may take the CU's whole LDS)
-        tmin = (EVAL_THREADS + D - 1) / D;               // >= one element per lane
-    }
-    if (tmax < 2) tmax = 2;
-    if (tmin > tmax) tmin = tmax;
-    int T;
-    if (d->tile_rows > 0) T = d->tile_rows < tmax ? d->tile_rows : tmax;
-    else {
-        // enough workgroups to cover 256 CUs a few times over
-        int want = (1024 + d->batch - 1) / d->batch;     // tiles per seed
-        T = N / (want > 0 ? want : 1);
-        if (T < tmin) T = tmin;
-        if (T > tmax) T = tmax;
-    }
-    if (T > N) T = N;
-    if (sh && (T & 1)) T += (T + 1 <= tmax) ? 1 : -1;
-    if (T < 2) T = 2;
-    dm.T = T;
-    dm.ntiles = (N + T - 1) / T;
 }
 
 // per-seed vectors, L-BFGS history, partial tables and result tables: the part of the device
@@ -629,6 +394,48 @@ int fetch_table(va_handle h, const T *dev, T *host, int nbeta, int per)
     return VA_OK;
 }
 
+// Why a problem of a module in column-parameter form cannot run that form (the module then has no kernel for it when it has
+// more than RHS_BIG_NP parameters): the first reason that applies.
+void colp_refusal(const va_problem_desc *d, const ModuleVariant &mv, char *msg, size_t n)
+{
+    if (const char *flat_only = flat_only_reason(d)) snprintf(msg, n, "%s", flat_only);
+    else if (d->D > 64 && (d->D & 1)) snprintf(msg, n, "odd D = %d > 64 (k_eval3, which has no column-parameter form)", d->D);
+    else if (d->D > 64 && mv.kernel != 5) snprintf(msg, n, "a non-autonomous model (model time or stimulus) on the streaming kernel k_eval5");
+    else if (d->D <= 64 && !tile4_ok(d->D)) snprintf(msg, n, "D = %d fits neither k_eval4 (even D <= 64 filling a wave) nor k_eval5", d->D);
+    else if (d->eval_kernel != 0 && d->eval_kernel != mv.kernel) snprintf(msg, n, "eval_kernel = %d (the module carries kernel %d)", d->eval_kernel, mv.kernel);
+    else snprintf(msg, n, "the module's column-run instantiation does not fit this problem (weights, discretisation or run length): regenerate it");
+}
+
+// The plan of a problem that comes with a generated module.  The module holds ONE instantiation of a column-run kernel
+// (va_eval_plan named it when the module was generated): `variant` says whether the problem runs it, with cps shared scalars
+// and cpv vector entries when it is of the column-parameter form; a problem that calls for any other geometry runs the
+// module's flat kernel.  VA_OK, or the refusal of a problem no kernel of the module carries.
+struct ModulePlan {
+    EvalPlan plan;
+    bool variant = false;
+    int cps = 0, cpv = 0;
+};
+int plan_module(const va_problem_desc *d, const UserRhs &u, ModulePlan &mp)
+{
+    const ModuleVariant &mv = u.variant;
+    // more than RHS_MAX_NP parameters: the flat kernel carries them (their gradient partials in a table of their own), or
+    // a column-parameter form, which carries any number: its vectors' partials have a table of their own
+    const bool bigp = d->NP > RHS_MAX_NP;
+    mp.plan = plan_eval(d, bigp && !mv.column_params() ? mv.flat_form() : mv.form());
+    mp.variant = mp.plan.emode != 1 && variant_key(mp.plan, d) == mv.key();
+    if (!mp.variant && mp.plan.emode != 1) mp.plan = plan_eval(d, mv.flat_form());
+    if (mp.variant && mv.column_params()) { mp.cps = u.colp[0]; mp.cpv = u.colp[1] * d->D; }
+    if (d->NP > RHS_BIG_NP && !mp.cpv) {
+        char why[192];
+        colp_refusal(d, mv, why, sizeof why);
+        return fail(VA_EUNSUPPORTED, "%d parameters: only the column-parameter form on k_eval4 / k_eval5 carries more than %d, "
+                                     "and this problem cannot run it: %s", d->NP, RHS_BIG_NP, why);
+    }
+    if (mp.plan.emode == 4 && mp.cpv > mp.plan.g4.XW)       // (k_eval4 leaves the vector partials in the wave's x image)
+        return fail(VA_EUNSUPPORTED, "runs of %d rows are too short for %d vector entries on k_eval4", mp.plan.g4.K, mp.cpv);
+    return VA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -651,17 +458,12 @@ int va_eval_plan_reach(const va_problem_desc *d, int32_t ne, int32_t ghost, cons
     if (d->struct_size != (int32_t)sizeof(va_problem_desc)) return fail(VA_EINVAL, "struct_size %d != %zu", d->struct_size, sizeof(va_problem_desc));
     out[0] = out[1] = out[2] = out[3] = 0;
     if ((ne <= 0 && ghost <= 0) || d->D < 1 || d->N_model < 2 || d->batch < 1) return VA_OK;
-    Dims dm{};
-    Geo4 g4{};
-    Geo5 g5{};
-    std::vector<int> ys;
-    int r5[4] = {0, 0, 0, 0};
-    if (reach) for (int k = 0; k < 4; ++k) r5[k] = reach[k];
     if (d->L > 0 && !d->Lidx) return fail(VA_EINVAL, "Lidx is NULL");
-    pick_eval_geometry(d, dm, g4, ne, ghost, reach ? r5 : nullptr, &g5, &ys);
-    if (dm.emode != 3 && dm.emode != 4 && dm.emode != 5) return VA_OK;
-    out[0] = dm.emode; out[1] = d->disc; out[2] = dm.emode == 5 ? 0 : dm.maxr;
-    out[3] = dm.emode == 4 ? ((d->rm_kind == 0 && d->rf_kind == 0 && d->merr_nskip == 1) ? 1 : 0) : (dm.emode == 5 ? 0 : dm.NT);
+    EvalForm form;
+    form.ne = ne; form.ghost = ghost; form.has_reach5 = reach != nullptr;
+    if (reach) for (int k = 0; k < 4; ++k) form.reach5[k] = reach[k];
+    const VariantKey key = variant_key(plan_eval(d, form), d);
+    out[0] = key.kernel; out[1] = key.disc; out[2] = key.K; out[3] = key.W;
     return VA_OK;
 }
 
@@ -686,18 +488,21 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
     u.prepare = (int (*)(const Dev *))dlsym(u.dl, "va_user_prepare_eval");
     u.seed_kernel = (int (*)(const Dev *, int, void *))dlsym(u.dl, "va_user_seed_kernel");
     if (!info || !u.launch || !u.prepare) { dlclose(u.dl); return fail(VA_EINVAL, "%s lacks va_user_rhs_info / va_user_launch_eval / va_user_prepare_eval", path); }
-    int v[5] = {0, 0, 0, 0, 0};
-    info(v);
-    if (v[3] != (int)sizeof(Dev) || v[4] != (int)sizeof(SeedState)) {
+    int ri[5] = {0, 0, 0, 0, 0};           // (NP, D, NSTIM, sizeof(Dev), sizeof(SeedState))
+    info(ri);
+    const int dev_bytes = ri[3], seed_bytes = ri[4];
+    if (dev_bytes != (int)sizeof(Dev) || seed_bytes != (int)sizeof(SeedState)) {
         dlclose(u.dl);
-        return fail(VA_EINVAL, "%s was built against different headers (Dev %d vs %zu bytes): rebuild it", path, v[3], sizeof(Dev));
+        return fail(VA_EINVAL, "%s was built against different headers (Dev %d vs %zu bytes): rebuild it", path, dev_bytes, sizeof(Dev));
     }
-    u.NP = v[0]; u.D = v[1]; u.NSTIM = v[2];
-    if (info_fn vinfo = (info_fn)dlsym(u.dl, "va_user_variant_info")) {        // (writes 12 ints)
-        vinfo(u.var);
+    u.NP = ri[0]; u.D = ri[1]; u.NSTIM = ri[2];
+    if (info_fn vinfo = (info_fn)dlsym(u.dl, "va_user_variant_info")) {
+        int uv[UV_N];
+        vinfo(uv);
+        u.variant = ModuleVariant::decode(uv);
         u.launch_var = (void (*)(const Dev *, void *))dlsym(u.dl, "va_user_launch_variant");
         u.prepare_var = (int (*)(const Dev *))dlsym(u.dl, "va_user_prepare_variant");
-        if (!u.launch_var || !u.prepare_var) u.var[0] = 0;
+        if (!u.launch_var || !u.prepare_var) u.variant.kernel = 0;
     }
     if (info_fn cmap = (info_fn)dlsym(u.dl, "va_user_colp_map")) {
         // (S <= RHS_MAX_NP and V <= CP_VMAX by construction: the generator checks both)
@@ -705,12 +510,12 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
         cmap(u.colp.data());
         u.colp.resize(2 + (size_t)u.colp[0] + (size_t)u.colp[1] * u.D);
     }
-    if (u.colp.empty()) u.var[11] = 0;
+    if (u.colp.empty()) u.variant.n_colp_vectors = 0;
     // past RHS_BIG_NP parameters a module has no flat kernel: it must carry the column-parameter form (the kernels that
     // run it are checked problem by problem, va_problem_create)
-    if (v[0] < 0 || (v[0] > RHS_BIG_NP && u.colp.empty())) {
+    if (u.NP < 0 || (u.NP > RHS_BIG_NP && u.colp.empty())) {
         dlclose(u.dl);
-        return fail(VA_EUNSUPPORTED, "%s: NP=%d > %d and no column-parameter form", path, v[0], RHS_BIG_NP);
+        return fail(VA_EUNSUPPORTED, "%s: NP=%d > %d and no column-parameter form", path, u.NP, RHS_BIG_NP);
     }
     g_user_rhs.push_back(u);
     *rhs_id = VA_RHS_USER_BASE + (int32_t)g_user_rhs.size() - 1;
@@ -731,29 +536,15 @@ int va_act_load_module(const char *path, int32_t *act_id)
     info_fn info = (info_fn)dlsym(u.dl, "va_user_act_info");
     u.launch = (NnetActLaunch)dlsym(u.dl, "va_user_act_launch");
     if (!info || !u.launch) { dlclose(u.dl); return fail(VA_EINVAL, "%s lacks va_user_act_info / va_user_act_launch", path); }
-    int v[3] = {0, 0, 0};
-    info(v);
-    if (v[0] != (int)sizeof(Dev) || v[1] != (int)sizeof(NnetDev) || v[2] != (int)sizeof(SeedState)) {
+    int ai[3] = {0, 0, 0};                 // (sizeof(Dev), sizeof(NnetDev), sizeof(SeedState))
+    info(ai);
+    if (ai[0] != (int)sizeof(Dev) || ai[1] != (int)sizeof(NnetDev) || ai[2] != (int)sizeof(SeedState)) {
         dlclose(u.dl);
         return fail(VA_EINVAL, "%s was built against different headers: rebuild it", path);
     }
     g_user_act.push_back(u);
     *act_id = VA_ACT_USER_BASE + (int32_t)g_user_act.size() - 1;
     return VA_OK;
-}
-
-// Why a problem of a module in column-parameter form cannot run that form (the module then has no kernel for it when it has
-// more than RHS_BIG_NP parameters): the first reason that applies.
-static void colp_refusal(const va_problem_desc *d, const UserRhs *u, char *msg, size_t n)
-{
-    if (d->lower && d->upper) snprintf(msg, n, "box bounds (carried by the flat kernel only)");
-    else if (d->p_time_dependent) snprintf(msg, n, "time-dependent parameters");
-    else if (d->rm_kind == 2 || d->rf_kind == 2) snprintf(msg, n, "full RM / RF matrices (flat kernel only)");
-    else if (d->D > 64 && (d->D & 1)) snprintf(msg, n, "odd D = %d > 64 (k_eval3, which has no column-parameter form)", d->D);
-    else if (d->D > 64 && u->var[0] != 5) snprintf(msg, n, "a non-autonomous model (model time or stimulus) on the streaming kernel k_eval5");
-    else if (d->D <= 64 && !tile4_ok(d->D)) snprintf(msg, n, "D = %d fits neither k_eval4 (even D <= 64 filling a wave) nor k_eval5", d->D);
-    else if (d->eval_kernel != 0 && d->eval_kernel != u->var[0]) snprintf(msg, n, "eval_kernel = %d (the module carries kernel %d)", d->eval_kernel, u->var[0]);
-    else snprintf(msg, n, "the module's column-run instantiation does not fit this problem (weights, discretisation or run length): regenerate it");
 }
 
 int va_problem_create(const va_problem_desc *d, va_handle *out)
@@ -842,44 +633,26 @@ int va_problem_create(const va_problem_desc *d, va_handle *out)
     dm.bounded = (d->lower && d->upper) ? 1 : 0;
     if (tdp) { dm.ND = dm.N * (dm.D + dm.NPe); dm.NP = 0; dm.NPest = 0; }   // one flat run for the L-BFGS kernels
     dm.ld = ((dm.ND + dm.NPest + 15) / 16) * 16;
-    std::vector<int> ystrip_h;
+    EvalPlan plan;
     if (!user) {
-        const int reach5[4] = {t5_xl<RhsL96s>(), t5_xr<RhsL96s>(), t5_gl<RhsL96s>(), t5_gr<RhsL96s>()};
-        pick_eval_geometry(d, dm, dv.g4, RhsL96s::NE, RhsL96g::GHOST, reach5, &dv.g5, &ystrip_h);
+        EvalForm l96;
+        l96.ne = RhsL96s::NE; l96.ghost = RhsL96g::GHOST; l96.has_reach5 = true;
+        l96.reach5[0] = t5_xl<RhsL96s>(); l96.reach5[1] = t5_xr<RhsL96s>(); l96.reach5[2] = t5_gl<RhsL96s>(); l96.reach5[3] = t5_gr<RhsL96s>();
+        plan = plan_eval(d, l96);
     }
     else {
-        // the module holds ONE instantiation of a column-run kernel (va_eval_plan named it when the module
-        // was generated); a problem that calls for any other geometry runs the module's flat kernel
-        const int *v = user->var;
-        dm.lin = v[10] ? 1 : 0;
-        // (a column-parameter form carries any number of parameters: its vectors' partials have a table of their own)
-        const bool cpvar = v[11] > 0 && (v[0] == 4 || v[0] == 5);
-        if (bigp && !cpvar) pick_eval_geometry(d, dm, dv.g4, 0, 0);
-        else pick_eval_geometry(d, dm, dv.g4, (v[0] == 4 || v[0] == 5) ? v[4] : 0, v[0] == 3 ? v[5] : 0, v[0] == 5 ? v + 6 : nullptr, &dv.g5, &ystrip_h);
-        const bool ws = d->rm_kind == 0 && d->rf_kind == 0 && d->merr_nskip == 1;
-        const bool fits = dm.emode == v[0] && v[1] == d->disc &&
-                          (dm.emode == 5 ? true : (v[2] == dm.maxr && (dm.emode == 4 ? (v[3] != 0) == ws : v[3] == dm.NT)));
-        if (dm.emode != 1 && fits) {
-            h->user_launch = user->launch_var; h->user_prepare = user->prepare_var;
-            if (cpvar) {
-                dv.cps = user->colp[0]; dv.cpv = user->colp[1] * dm.D;
-                dv.cpnsg = dm.emode == 5 ? dv.g5.NSG : 0;
-            }
-        }
-        else if (dm.emode != 1) pick_eval_geometry(d, dm, dv.g4, 0, 0);
-        if (noflat && !dv.cpv) {
-            char why[192];
-            colp_refusal(d, user, why, sizeof why);
-            va_problem_destroy(h);
-            return fail(VA_EUNSUPPORTED, "%d parameters: only the column-parameter form on k_eval4 / k_eval5 carries more than %d, "
-                                         "and this problem cannot run it: %s", d->NP, RHS_BIG_NP, why);
-        }
-        if (dm.emode == 4 && dv.cpv > dv.g4.XW) {       // (k_eval4 leaves the vector partials in the wave's x image)
-            const int K = dv.g4.K;
-            va_problem_destroy(h);
-            return fail(VA_EUNSUPPORTED, "runs of %d rows are too short for %d vector entries on k_eval4", K, dv.cpv);
-        }
+        ModulePlan mp;
+        if (int rc = plan_module(d, *user, mp)) { va_problem_destroy(h); return rc; }
+        plan = mp.plan;
+        dm.lin = user->variant.has_linear;
+        if (mp.variant) { h->user_launch = user->launch_var; h->user_prepare = user->prepare_var; }
+        dv.cps = mp.cps; dv.cpv = mp.cpv;
+        dv.cpnsg = (mp.cpv && plan.emode == 5) ? plan.g5.NSG : 0;
     }
+    dm.emode = plan.emode; dm.RY = plan.RY; dm.NT = plan.NT; dm.maxr = plan.maxr; dm.T = plan.T; dm.ntiles = plan.ntiles;
+    dm.ghost = plan.ghost;
+    dv.g4 = plan.g4; dv.g5 = plan.g5;
+    const std::vector<int> &ystrip_h = plan.ystrip;
     if (dm.emode == 4 && (unsigned long long)dm.B * dm.ntiles * dm.ntiles >= (1ull << 32)) {
         va_problem_destroy(h);        // (umulhi by ntiles_magic would no longer be an exact division)
         return fail(VA_EUNSUPPORTED, "batch x tiles too large for the wave-private kernel: pass eval_kernel=3");

@@ -43,6 +43,7 @@ enum { UPD_X = 1, UPD_G = 2, UPD_HIST = 4, UPD_STORE = 8 };
 enum { LS_START = 0, LS_FG = 1, LS_CONV = 2, LS_WARN = 3, LS_ERROR = 4 };
 
 constexpr int MAX_M = 32;        // history pairs
+constexpr int EVAL_THREADS = 256;    // the flat evaluation kernel: 4 waves per workgroup
 constexpr int RHS_MAX_NP = 24;   // parameters the tuned kernels and the rows of partial sums carry (NaKL: 18)
 constexpr int RHS_BIG_NP = 128;  // parameters a right-hand side may have on the flat kernel: the gradient partials of those
                                  // beyond RHS_MAX_NP travel in a table of their own (Dev::evp_big); the reference has no cap
@@ -124,6 +125,20 @@ struct SeedState : SeedHot {
     double cY[MAX_M], cS[MAX_M];
     double a[MAX_M], b[MAX_M];
     double SY[MAX_M * MAX_M], YY[MAX_M * MAX_M];
+};
+
+// The integers a generated module's va_user_variant_info writes (va_user_rhs.hip) and the library decodes
+// (ModuleVariant, va_eval_geo.h): the ONE column-run instantiation the module carries besides its flat kernel.
+enum {
+    UV_KERNEL = 0,      // eval kernel 3 / 4 / 5, or 0: none
+    UV_DISC = 1, UV_K = 2,
+    UV_W = 3,           // kernel 4: scalar weights; kernel 3: threads per workgroup
+    UV_NE = 4,          // products per element of the column form [4, 5]
+    UV_GHOST = 5,       // ghost columns of the ghosted form [3]
+    UV_REACH = 6,       // the column form's reaches xl, xr, gl, gr [5]
+    UV_LINEAR = 10,     // the flat kernel carries a dense linear part
+    UV_NCV = 11,        // vectors of the column-parameter form, when the instantiation is of that form
+    UV_N = 12
 };
 
 // ---------------------------------------------------------------- RHS: Lorenz-96

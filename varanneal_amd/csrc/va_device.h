@@ -10,7 +10,6 @@
 
 namespace va {
 
-constexpr int EVAL_THREADS = 256;    // 4 waves per workgroup
 constexpr int VEC_THREADS = 256;
 constexpr int VEC_CHUNK = 1024;      // elements of a seed's vector per workgroup (2 x double2 per lane)
 

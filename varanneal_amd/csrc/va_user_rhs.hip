@@ -67,8 +67,7 @@ int va_user_seed_kernel(const va::Dev *dv, int launch, void *stream)
 //   EK = 3: a stencil's ghosted form (struct RhsUserG) on the workgroup kernel k_eval3; W = threads per workgroup
 // A model in column-parameter form (struct RhsUserColP: a stencil with per-column parameter vectors) takes the place of
 // the column form for EK = 4 and 5.
-// (eval kernel or 0, DISC, K, W, products per element [4, 5], ghost columns [3], reaches xl, xr, gl, gr [5], dense linear
-// part, vectors of the column-parameter form)
+// (the integers are named in va_core.h: UV_*)
 #if defined(VA_USER_COLP)
 #define VA_USER_COLT va::RhsUserColP
 #elif defined(VA_USER_COL)
@@ -83,20 +82,20 @@ int va_user_seed_kernel(const va::Dev *dv, int launch, void *stream)
 #endif
 void va_user_variant_info(int *out)
 {
-    for (int k = 0; k < 12; ++k) out[k] = 0;
-    out[10] = va::rhs_linear<va::RhsUser>::value ? 1 : 0;     // the flat kernel stages one more array (va_eval_flat.h lin_gemm)
+    for (int k = 0; k < va::UV_N; ++k) out[k] = 0;
+    out[va::UV_LINEAR] = va::rhs_linear<va::RhsUser>::value ? 1 : 0;     // the flat kernel stages one more array (va_eval_flat.h lin_gemm)
 #ifdef VA_USER_VARIANT
-    out[0] = VA_USER_VARIANT; out[1] = VA_USER_DISC; out[2] = VA_USER_K; out[3] = VA_USER_W;
+    out[va::UV_KERNEL] = VA_USER_VARIANT; out[va::UV_DISC] = VA_USER_DISC; out[va::UV_K] = VA_USER_K; out[va::UV_W] = VA_USER_W;
 #if VA_USER_VARIANT == 5
-    out[4] = VA_USER_COLT::NE;
-    out[6] = va::t5_xl<VA_USER_COLT>(); out[7] = va::t5_xr<VA_USER_COLT>();
-    out[8] = va::t5_gl<VA_USER_COLT>(); out[9] = va::t5_gr<VA_USER_COLT>();
-    out[11] = va::rhs_ncv<VA_USER_COLT>::value;
+    out[va::UV_NE] = VA_USER_COLT::NE;
+    out[va::UV_REACH] = va::t5_xl<VA_USER_COLT>(); out[va::UV_REACH + 1] = va::t5_xr<VA_USER_COLT>();
+    out[va::UV_REACH + 2] = va::t5_gl<VA_USER_COLT>(); out[va::UV_REACH + 3] = va::t5_gr<VA_USER_COLT>();
+    out[va::UV_NCV] = va::rhs_ncv<VA_USER_COLT>::value;
 #elif VA_USER_VARIANT == 4
-    out[4] = VA_USER_COLT::NE;
-    out[11] = va::rhs_ncv<VA_USER_COLT>::value;
+    out[va::UV_NE] = VA_USER_COLT::NE;
+    out[va::UV_NCV] = va::rhs_ncv<VA_USER_COLT>::value;
 #else
-    out[5] = va::RhsUserG::GHOST;
+    out[va::UV_GHOST] = va::RhsUserG::GHOST;
 #endif
 #endif
 }
