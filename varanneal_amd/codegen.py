@@ -950,7 +950,7 @@ def activation_header(g, dg, z, name="act"):
 
 def _act_fingerprint():
     h = hashlib.sha1(BUILD_TAG.encode())
-    for fn in ("va_core.h", "va_device.h", "va_eval_flat.h", "va_epilogue.h", "va_nnet.h", "va_nnet_kernels.h",
+    for fn in ("va_core.h", "va_device.h", "va_eval_flat.h", "va_epilogue.h", "va_nnet.h", "va_nnet_geo.h", "va_nnet_kernels.h",
                "va_user_act.hip"):
         with open(os.path.join(CSRC, fn), "rb") as fh:
             h.update(fh.read())

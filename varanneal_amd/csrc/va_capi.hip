@@ -5,6 +5,19 @@
 //     k_eval (+ line-search / ladder step) -> k_update (+ direction coefficients) -> k_direction
 // until every seed has climbed its whole RF ladder.  No per-iteration host sync:
 // the host only polls a device counter of unfinished seeds every few cycles.
+//
+// Creation.  A handle under construction has ONE owner (HandleOwner: va_problem_destroy on every way out but success), and
+// both constructors share their front and back halves:
+//     begin_create         device, stream, zeroed Dev, lbfgs_m / max_beta, default options
+//     ... the action's own steps ...
+//     alloc_solver_state   per-seed vectors, L-BFGS history, result tables
+//     finish_create        pinned poll word, events, the stream sync that ends the life of the host staging buffers
+// va_problem_create:       validate_desc (every check that needs neither HIP nor the plan) -> begin_create -> plan_problem
+//                          (plan_eval / plan_module, va_eval_geo.h) -> fill_dims (Dims / Dev from the descriptor and the
+//                          plan) -> prepare_kernels (LDS check, opt-in) -> alloc_problem_data -> alloc_solver_state ->
+//                          upload_problem_data -> choose_persist -> finish_create
+// va_nnet_problem_create:  plan_nnet (va_nnet_geo.h: the descriptor's checks and the whole launch plan, host arithmetic a
+//                          CPU test records) -> begin_create -> fill_nnet_dims -> create_nnet_image -> finish_create
 #include <dlfcn.h>
 #include <link.h>
 #include <stdarg.h>
@@ -13,6 +26,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -48,6 +62,14 @@ int fail(int code, const char *fmt, ...)
             return fail(e_ == hipErrorOutOfMemory ? VA_ENOMEM : VA_EHIP, "%s: %s (%s:%d)", \
                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                 \
     } while (0)
+
+// a step that returns a code: pass the first failure on
+#define TRY(expr)                       \
+    do {                                \
+        if (int rc_ = (expr)) return rc_; \
+    } while (0)
+// an upload into a handle's buffer, whose name a failure reports
+#define UPLOAD(dst, src, n) h->upload(dst, src, n, #dst)
 
 // generated right-hand-side modules (va_rhs_load_module); ids are VA_RHS_USER_BASE + index
 struct UserRhs {
@@ -116,7 +138,20 @@ struct va_problem_s {
         *p = (T *)q;
         return VA_OK;
     }
+    // n elements host -> device on the handle's stream.  Asynchronous, and from pageable memory during creation: src stays
+    // untouched until the stream is synchronised (finish_create)
+    template <class T> int upload(T *dst, const T *src, size_t n, const char *name)
+    {
+        hipError_t e = hipMemcpyAsync(dst, src, sizeof(T) * n, hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) return fail(VA_EHIP, "H2D %s: %s", name, hipGetErrorString(e));
+        return VA_OK;
+    }
 };
+
+// the one owner of a handle under construction: whatever way a constructor returns before `*out = h.release()`, the
+// handle and everything it allocated so far go through va_problem_destroy
+struct HandleDeleter { void operator()(va_problem_s *h) const { va_problem_destroy(h); } };
+typedef std::unique_ptr<va_problem_s, HandleDeleter> HandleOwner;
 
 namespace {
 
@@ -146,44 +181,41 @@ void run_eval(va_handle h, int epi)
 
 // per-seed vectors, L-BFGS history, partial tables and result tables: the part of the device
 // image that does not depend on which action is being minimised
-int alloc_solver_state(va_handle h, int max_beta, int keep_paths)
+int alloc_solver_state(va_handle h)
 {
     Dev &dv = h->dv;
     const Dims &dm = dv.dm;
-    const size_t B = dm.B, ld = dm.ld, m = dm.m;
-    int rc;
-#define TRYA(x) do { rc = (x); if (rc) return rc; } while (0)
+    const size_t B = dm.B, ld = dm.ld, m = dm.m, max_beta = dv.max_beta;
     // x and d carry a zero-filled guard in front and behind: the evaluation kernels stage whole
     // tiles (+ halo rows) without clamping, so the first / last tile of the first / last seed reads
     // up to one tile beyond its path (such rows are masked out of the arithmetic)
     const size_t guard = (((size_t)(dm.T + 8) * dm.D + 15) / 16) * 16;
-    TRYA(h->alloc(&dv.x, B * ld + 2 * guard)); TRYA(h->alloc(&dv.g, B * ld));
-    TRYA(h->alloc(&dv.gt, B * ld)); TRYA(h->alloc(&dv.d, B * ld + 2 * guard));
+    TRY(h->alloc(&dv.x, B * ld + 2 * guard)); TRY(h->alloc(&dv.g, B * ld));
+    TRY(h->alloc(&dv.gt, B * ld)); TRY(h->alloc(&dv.d, B * ld + 2 * guard));
     dv.x += guard; dv.d += guard;
-    TRYA(h->alloc(&dv.S, B * m * ld)); TRYA(h->alloc(&dv.Y, B * m * ld));
-    TRYA(h->alloc(&dv.st, B));
-    TRYA(h->alloc(&dv.evp, B * dm.nprow * EP_N));
+    TRY(h->alloc(&dv.S, B * m * ld)); TRY(h->alloc(&dv.Y, B * m * ld));
+    TRY(h->alloc(&dv.st, B));
+    TRY(h->alloc(&dv.evp, B * dm.nprow * EP_N));
     dv.npbig = (!h->is_nnet && !dv.cpv && dm.NPt > RHS_MAX_NP) ? dm.NPt - RHS_MAX_NP : 0;
-    if (dv.npbig) TRYA(h->alloc(&dv.evp_big, B * dm.nprow * dv.npbig));
-    if (dv.cpv) TRYA(h->alloc(&dv.evv, B * dm.nprow * dv.cpv));
-    TRYA(h->alloc(&dv.upp, B * dm.nchunks * dv.ups));
-    TRYA(h->alloc(&dv.dpp, B * dm.nchunks * DP_N));
-    TRYA(h->alloc(&h->d_rf, (size_t)max_beta));
-    TRYA(h->alloc(&dv.ame, B * max_beta * 3));
-    TRYA(h->alloc(&dv.pest, B * max_beta * (dm.NPest ? dm.NPest : 1)));
-    TRYA(h->alloc(&dv.status, B * max_beta)); TRYA(h->alloc(&dv.nit, B * max_beta));
-    TRYA(h->alloc(&dv.nfev, B * max_beta));
-    if (keep_paths) TRYA(h->alloc(&dv.minpaths, B * max_beta * (size_t)(dm.ND + dm.NP), false));
+    if (dv.npbig) TRY(h->alloc(&dv.evp_big, B * dm.nprow * dv.npbig));
+    if (dv.cpv) TRY(h->alloc(&dv.evv, B * dm.nprow * dv.cpv));
+    TRY(h->alloc(&dv.upp, B * dm.nchunks * dv.ups));
+    TRY(h->alloc(&dv.dpp, B * dm.nchunks * DP_N));
+    TRY(h->alloc(&h->d_rf, max_beta));
+    TRY(h->alloc(&dv.ame, B * max_beta * 3));
+    TRY(h->alloc(&dv.pest, B * max_beta * (dm.NPest ? dm.NPest : 1)));
+    TRY(h->alloc(&dv.status, B * max_beta)); TRY(h->alloc(&dv.nit, B * max_beta));
+    TRY(h->alloc(&dv.nfev, B * max_beta));
+    if (h->keep_paths) TRY(h->alloc(&dv.minpaths, B * max_beta * (size_t)(dm.ND + dm.NP), false));
     if (dm.bounded) {
-        TRYA(h->alloc(&dv.lb_z, B * ld)); TRYA(h->alloc(&dv.lb_r, B * ld)); TRYA(h->alloc(&dv.lb_xp, B * ld));
-        TRYA(h->alloc(&dv.lb_t, B * ld)); TRYA(h->alloc(&dv.lb_iwhere, B * ld));
-        TRYA(h->alloc(&dv.lb_mat, B * 3 * m * m)); TRYA(h->alloc(&dv.lb_dtd, B));
+        TRY(h->alloc(&dv.lb_z, B * ld)); TRY(h->alloc(&dv.lb_r, B * ld)); TRY(h->alloc(&dv.lb_xp, B * ld));
+        TRY(h->alloc(&dv.lb_t, B * ld)); TRY(h->alloc(&dv.lb_iwhere, B * ld));
+        TRY(h->alloc(&dv.lb_mat, B * 3 * m * m)); TRY(h->alloc(&dv.lb_dtd, B));
     }
-    TRYA(h->alloc(&dv.cnt_eval, B * CNT_STRIDE)); TRYA(h->alloc(&dv.cnt_upd, B * CNT_STRIDE)); TRYA(h->alloc(&dv.cnt_dir, B * CNT_STRIDE));
-    TRYA(h->alloc(&dv.n_active, 1));
-    TRYA(h->alloc(&dv.n_evals, 1));
-    TRYA(h->alloc(&dv.outA, B)); TRYA(h->alloc(&dv.outme, B)); TRYA(h->alloc(&dv.outfe, B));
-#undef TRYA
+    TRY(h->alloc(&dv.cnt_eval, B * CNT_STRIDE)); TRY(h->alloc(&dv.cnt_upd, B * CNT_STRIDE)); TRY(h->alloc(&dv.cnt_dir, B * CNT_STRIDE));
+    TRY(h->alloc(&dv.n_active, 1));
+    TRY(h->alloc(&dv.n_evals, 1));
+    TRY(h->alloc(&dv.outA, B)); TRY(h->alloc(&dv.outme, B)); TRY(h->alloc(&dv.outfe, B));
     dv.rf_ladder = h->d_rf;
     return VA_OK;
 }
@@ -264,6 +296,48 @@ bool profiler_attached()
     return attached;
 }
 
+// the most cycles a ladder of nbeta rungs may take: every cycle costs each live seed at least one evaluation
+long long ladder_cycle_bound(const Dev &dv, int nbeta)
+{
+    const double per_step = (double)dv.o.maxfun + dv.o.maxls + 4.0;
+    const double bound = per_step * nbeta;
+    return bound > 4e18 ? (long long)4e18 : (long long)bound;
+}
+
+// the ladder on the device, every seed counted live and put in PH_START (zero_dpp: the three-launch cycle's direction
+// partials are zeroed where they always were on the stream, ahead of the state kernel)
+int arm_ladder(va_handle h, const double *rf_scale, int nbeta, bool zero_dpp)
+{
+    Dev &dv = h->dv;
+    HIPCHK(hipMemcpyAsync(h->d_rf, rf_scale, sizeof(double) * nbeta, hipMemcpyHostToDevice, h->stream));
+    dv.nbeta = nbeta; h->last_nbeta = nbeta;
+    *h->h_nactive = dv.dm.B;
+    HIPCHK(hipMemcpyAsync(dv.n_active, h->h_nactive, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (zero_dpp) HIPCHK(hipMemsetAsync(dv.dpp, 0, sizeof(double) * dv.dm.B * dv.dm.nchunks * DP_N, h->stream));
+    launch_init_states(dv, PH_START, -1.0, h->stream);
+    h->timed_armed_rf = -1.0;
+    return VA_OK;
+}
+
+// the count of live seeds and the evaluation counter into the pinned words (and 16 bytes of the persistent kernel's
+// flags into misc, if given); returns once they are there
+int read_progress(va_handle h, void *misc = nullptr)
+{
+    const Dev &dv = h->dv;
+    HIPCHK(hipMemcpyAsync(h->h_nactive, dv.n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_nactive + 2, dv.n_evals, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    if (misc) HIPCHK(hipMemcpyAsync(misc, h->pz_misc, 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return VA_OK;
+}
+
+// a ladder ended after cyc cycles: the handle's counters, from what read_progress left
+void book_ladder(va_handle h, long long cyc)
+{
+    h->n_cycles += cyc; h->n_eval_launch += cyc;
+    h->n_seed_evals = h->n_seed_evals_direct + (int64_t)*(unsigned long long *)(h->h_nactive + 2);
+}
+
 // the kernel cycle until no seed is left (or the evaluation budget bound is hit)
 int run_ladder_persist(va_handle h, const double *rf_scale, int nbeta, bool *fell_back);
 
@@ -276,18 +350,9 @@ int run_ladder(va_handle h, const double *rf_scale, int nbeta)
         const int rc = run_ladder_persist(h, rf_scale, nbeta, &fell_back);
         if (!fell_back) return rc;
     }
-    HIPCHK(hipMemcpyAsync(h->d_rf, rf_scale, sizeof(double) * nbeta, hipMemcpyHostToDevice, h->stream));
-    dv.nbeta = nbeta; h->last_nbeta = nbeta;
-    *h->h_nactive = dv.dm.B;
-    HIPCHK(hipMemcpyAsync(dv.n_active, h->h_nactive, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(dv.dpp, 0, sizeof(double) * dv.dm.B * dv.dm.nchunks * DP_N, h->stream));
-    launch_init_states(dv, PH_START, -1.0, h->stream);
-    h->timed_armed_rf = -1.0;
+    TRY(arm_ladder(h, rf_scale, nbeta, true));
     if (dv.dm.bounded) launch_clamp_x(dv, h->stream);
-    // every cycle costs each live seed at least one evaluation
-    const double per_step = (double)dv.o.maxfun + dv.o.maxls + 4.0;
-    const double bound = per_step * nbeta;
-    long long max_cycles = bound > 4e18 ? (long long)4e18 : (long long)bound;
+    const long long max_cycles = ladder_cycle_bound(dv, nbeta);
     long long cyc = 0;
     int poll = 4;
     // Long ladders on small problems are bound by the host's launch rate (3 launches per cycle at
@@ -323,15 +388,12 @@ int run_ladder(va_handle h, const double *rf_scale, int nbeta)
         } else enqueue(poll);
         cyc += poll;
         HIPCHK(hipGetLastError());            // a failed launch surfaces here, with its cause, not as a stalled ladder
-        HIPCHK(hipMemcpyAsync(h->h_nactive, dv.n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(h->h_nactive + 2, dv.n_evals, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        TRY(read_progress(h));
         if (*h->h_nactive <= 0) break;
         if (cyc > max_cycles) return fail(VA_ESTATE, "ladder did not finish within %lld cycles", max_cycles);
         if (poll < 64) poll *= 2;
     }
-    h->n_cycles += cyc; h->n_eval_launch += cyc;
-    h->n_seed_evals = h->n_seed_evals_direct + (int64_t)*(unsigned long long *)(h->h_nactive + 2);
+    book_ladder(h, cyc);
     HIPCHK(hipGetLastError());
     return VA_OK;
 }
@@ -342,20 +404,13 @@ int run_ladder_persist(va_handle h, const double *rf_scale, int nbeta, bool *fel
 {
     Dev &dv = h->dv;
     *fell_back = false;
-    const double per_step = (double)dv.o.maxfun + dv.o.maxls + 4.0;
-    const double bound = per_step * nbeta;
-    const long long max_cycles = bound > 4e18 ? (long long)4e18 : (long long)bound;
+    const long long max_cycles = ladder_cycle_bound(dv, nbeta);
     Dev dvp = dv;
     dvp.dm.T = h->pz_T; dvp.dm.ntiles = h->pz_G; dvp.dm.nprow = h->pz_G;
     dvp.nbeta = nbeta; dvp.pz.max_cycles = max_cycles;
     HIPCHK(hipMemsetAsync(dv.pz.xch, 0, h->pz_xch_bytes, h->stream));           // (tags restart at 1 with every launch)
     HIPCHK(hipMemsetAsync(h->pz_misc, 0, 16, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_rf, rf_scale, sizeof(double) * nbeta, hipMemcpyHostToDevice, h->stream));
-    dv.nbeta = nbeta; h->last_nbeta = nbeta;
-    *h->h_nactive = dv.dm.B;
-    HIPCHK(hipMemcpyAsync(dv.n_active, h->h_nactive, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    launch_init_states(dv, PH_START, -1.0, h->stream);
-    h->timed_armed_rf = -1.0;
+    TRY(arm_ladder(h, rf_scale, nbeta, false));
     const hipError_t e = h->user_seed ? (hipError_t)h->user_seed(&dvp, 1, (void *)h->stream) : seed_kernel_builtin(dvp, true, h->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -364,14 +419,9 @@ int run_ladder_persist(va_handle h, const double *rf_scale, int nbeta, bool *fel
         return VA_OK;
     }
     struct { int abort_flag, pad; unsigned long long cycles; } misc = {0, 0, 0ull};
-    HIPCHK(hipMemcpyAsync(h->h_nactive, dv.n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(h->h_nactive + 2, dv.n_evals, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(&misc, h->pz_misc, 16, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    TRY(read_progress(h, &misc));
     HIPCHK(hipGetLastError());
-    const long long cyc = (long long)(misc.cycles / (unsigned long long)(dv.dm.B > 0 ? 1 : 1));
-    h->n_cycles += cyc; h->n_eval_launch += cyc;
-    h->n_seed_evals = h->n_seed_evals_direct + (int64_t)*(unsigned long long *)(h->h_nactive + 2);
+    book_ladder(h, (long long)misc.cycles);
     if (misc.abort_flag == 1) {
         // a poll timed out: the seed's workgroups were not all resident.  Nothing was written back (x still holds the start
         // point, the result tables are rewritten from rung 0): this handle takes the three-launch cycle from now on
@@ -433,6 +483,420 @@ int plan_module(const va_problem_desc *d, const UserRhs &u, ModulePlan &mp)
     }
     if (mp.plan.emode == 4 && mp.cpv > mp.plan.g4.XW)       // (k_eval4 leaves the vector partials in the wave's x image)
         return fail(VA_EUNSUPPORTED, "runs of %d rows are too short for %d vector entries on k_eval4", mp.plan.g4.K, mp.cpv);
+    return VA_OK;
+}
+
+// ---------------------------------------------------------------- creation: the steps of the two constructors
+
+// The front half of both constructors: the device, a handle with its stream, a zeroed device image, the history length
+// and ladder capacity (their defaults), the default options.  Leaves h owning the handle, also when it fails.
+int begin_create(int device, void *stream, int lbfgs_m, int max_beta, int keep_paths, HandleOwner &h)
+{
+    const int m = lbfgs_m > 0 ? lbfgs_m : 10;
+    if (m > MAX_M) return fail(VA_EINVAL, "lbfgs_m=%d > %d", m, MAX_M);
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(VA_EINVAL, "device %d of %d", device, ndev);
+    HIPCHK(hipSetDevice(device));
+
+    h.reset(new va_problem_s());
+    h->device = device; h->keep_paths = keep_paths;
+    if (stream) h->stream = (hipStream_t)stream;
+    else {
+        hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+        if (e != hipSuccess) return fail(VA_EHIP, "hipStreamCreate: %s", hipGetErrorString(e));
+        h->own_stream = true;
+    }
+    Dev &dv = h->dv;
+    memset(&dv, 0, sizeof dv);
+    dv.dm.m = m;
+    dv.ups = UP_OLD + 4 * m; dv.max_beta = max_beta > 0 ? max_beta : 1; dv.nbeta = 1;
+    dv.o.m = m; dv.o.maxiter = 15000; dv.o.maxls = 20; dv.o.maxfun = 15000; dv.o.ftol = 2.2204460492503131e-09; dv.o.gtol = 1e-5;
+    return VA_OK;
+}
+
+// the padded length of a seed's vector and its chunks, once ND and NPest stand
+void set_ld(Dims &dm)
+{
+    dm.ld = ((dm.ND + dm.NPest + 15) / 16) * 16;
+    dm.chunk = VEC_CHUNK; dm.nchunks = (dm.ld + VEC_CHUNK - 1) / VEC_CHUNK;
+}
+
+// Step 1 of va_problem_create: every check of the descriptor that needs neither HIP nor the plan, the first that fails
+// first.  *user: the registered module the descriptor names (a copy: the registry may grow under another thread), or NULL.
+int validate_desc(const va_problem_desc *d, UserRhs &user_copy, const UserRhs **user)
+{
+    if (d->struct_size != (int32_t)sizeof(va_problem_desc)) return fail(VA_EINVAL, "struct_size %d != %zu", d->struct_size, sizeof(va_problem_desc));
+    if (d->batch < 1 || d->D < 1 || d->N_model < 2 || d->N_data < 1 || d->L < 0 || d->merr_nskip < 1)
+        return fail(VA_EINVAL, "bad sizes (batch=%d D=%d N_model=%d N_data=%d L=%d nskip=%d)", d->batch, d->D, d->N_model, d->N_data, d->L, d->merr_nskip);
+    if ((int64_t)(d->N_data - 1) * d->merr_nskip + 1 != d->N_model)      /* va_ode.py:557 */
+        return fail(VA_EINVAL, "N_model (%d) must equal (N_data-1)*merr_nskip+1 (%lld)", d->N_model,
+                    (long long)(d->N_data - 1) * d->merr_nskip + 1);
+    if (d->disc < VA_DISC_EULER || d->disc > VA_DISC_FORWARDMAP) return fail(VA_EINVAL, "unknown disc %d", d->disc);
+    if (d->disc == VA_DISC_SIMPSON_HERMITE && (d->N_model % 2) == 0)
+        return fail(VA_EINVAL, "SimpsonHermite needs an odd number of time points (N_model=%d)", d->N_model);
+    *user = nullptr;
+    if (d->rhs >= VA_RHS_USER_BASE) {
+        std::lock_guard<std::mutex> lock(g_user_rhs_mutex);
+        if ((size_t)(d->rhs - VA_RHS_USER_BASE) >= g_user_rhs.size()) return fail(VA_EINVAL, "rhs module id %d was never registered", d->rhs);
+        user_copy = g_user_rhs[d->rhs - VA_RHS_USER_BASE];
+        *user = &user_copy;
+        if (user_copy.NP != d->NP || user_copy.D != d->D || user_copy.NSTIM != d->n_stim)
+            return fail(VA_EINVAL, "rhs module %s was generated for D=%d NP=%d n_stim=%d, problem has D=%d NP=%d n_stim=%d",
+                        user_copy.path.c_str(), user_copy.D, user_copy.NP, user_copy.NSTIM, d->D, d->NP, d->n_stim);
+    } else if (d->rhs != VA_RHS_LORENZ96) return fail(VA_EUNSUPPORTED, "unknown built-in rhs %d", d->rhs);
+    if (d->rhs == VA_RHS_LORENZ96 && (d->NP != RhsL96::NP || d->D < 4))
+        return fail(VA_EINVAL, "Lorenz-96 needs NP=1 and D>=4 (NP=%d D=%d)", d->NP, d->D);
+    if (d->n_stim < 0 || (d->n_stim > 0 && !d->stim)) return fail(VA_EINVAL, "n_stim=%d without a stimulus array", d->n_stim);
+    // (more than RHS_BIG_NP parameters: a module in column-parameter form only, on k_eval4 / k_eval5 -- plan_module checks the kernel)
+    if (d->NP > RHS_BIG_NP && !(*user && !user_copy.colp.empty()))
+        return fail(VA_EUNSUPPORTED, "NP=%d > %d: only a generated module in column-parameter form (shared scalars + per-column "
+                                     "vectors) carries more, and this model has none", d->NP, RHS_BIG_NP);
+    if (d->NPest < 0 || d->NPest > d->NP) return fail(VA_EINVAL, "bad NP/NPest (%d/%d)", d->NP, d->NPest);
+    const bool tdp = d->p_time_dependent != 0;
+    // more than RHS_MAX_NP parameters: the flat kernel carries them (their gradient partials in a table of their own)
+    if (d->NP > RHS_MAX_NP && tdp) return fail(VA_EUNSUPPORTED, "time-dependent parameters: at most %d of them", RHS_MAX_NP);
+    if (tdp && d->disc != VA_DISC_TRAPEZOID && d->disc != VA_DISC_SIMPSON_HERMITE)
+        return fail(VA_EUNSUPPORTED, "time-dependent parameters: trapezoid and SimpsonHermite only (upstream's euler/forwardmap "
+                                     "branches are inconsistent, va_ode.py:345-349)");
+    if (tdp && (int64_t)d->N_model * (d->D + d->NPest) > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_var does not fit 32-bit indexing");
+    if (!d->Y || (d->L > 0 && !d->Lidx) || !d->P || (d->NPest > 0 && !d->Pidx)) return fail(VA_EINVAL, "null array in desc");
+    if ((d->rm_kind && !d->rm_array) || (d->rf_kind && !d->rf0_array)) return fail(VA_EINVAL, "rm/rf array kind without array");
+    if ((d->lower != nullptr) != (d->upper != nullptr)) return fail(VA_EINVAL, "lower and upper bounds come together");
+    std::vector<char> seen(d->D, 0);
+    for (int l = 0; l < d->L; ++l) {
+        if (d->Lidx[l] < 0 || d->Lidx[l] >= d->D) return fail(VA_EINVAL, "Lidx[%d]=%d outside [0,D)", l, d->Lidx[l]);
+        // any order is fine (data column l pairs with state column Lidx[l], va_ode.py:141); a state
+        // column observed twice has no slot in the column -> data-column map the kernels use
+        if (seen[d->Lidx[l]] && d->rm_kind != 2) return fail(VA_EUNSUPPORTED, "Lidx lists state column %d twice", d->Lidx[l]);
+        seen[d->Lidx[l]] = 1;
+    }
+    for (int k = 0; k < d->NPest; ++k)
+        if (d->Pidx[k] < 0 || d->Pidx[k] >= d->NP) return fail(VA_EINVAL, "Pidx[%d]=%d outside [0,NP)", k, d->Pidx[k]);
+    // (begin_create refuses it for both constructors; here it keeps its place ahead of the two checks that follow)
+    if (d->lbfgs_m > MAX_M) return fail(VA_EINVAL, "lbfgs_m=%d > %d", d->lbfgs_m, MAX_M);
+    if (d->rm_kind < 0 || d->rm_kind > 2) return fail(VA_EINVAL, "rm_kind %d", d->rm_kind);
+    if (d->lower) {
+        const int nv = tdp ? d->N_model * (d->D + d->NPest) : d->D * d->N_model + d->NPest;
+        for (int i = 0; i < nv; ++i)
+            if (!(d->lower[i] <= d->upper[i])) return fail(VA_EINVAL, "lower[%d] > upper[%d] (or NaN)", i, i);
+    }
+    return VA_OK;
+}
+
+// Step 2: the evaluation kernel and its geometry (va_eval_geo.h); for a generated module also which of its kernels the
+// handle launches and the sizes of its column-parameter form
+int plan_problem(va_handle h, const va_problem_desc *d, const UserRhs *user, EvalPlan &plan)
+{
+    Dev &dv = h->dv;
+    h->rhs = d->rhs;
+    if (!user) {
+        EvalForm l96;
+        l96.ne = RhsL96s::NE; l96.ghost = RhsL96g::GHOST; l96.has_reach5 = true;
+        l96.reach5[0] = t5_xl<RhsL96s>(); l96.reach5[1] = t5_xr<RhsL96s>(); l96.reach5[2] = t5_gl<RhsL96s>(); l96.reach5[3] = t5_gr<RhsL96s>();
+        plan = plan_eval(d, l96);
+        return VA_OK;
+    }
+    ModulePlan mp;
+    TRY(plan_module(d, *user, mp));
+    plan = mp.plan;
+    h->user_launch = mp.variant ? user->launch_var : user->launch;
+    h->user_prepare = mp.variant ? user->prepare_var : user->prepare;
+    h->user_seed = user->seed_kernel;
+    dv.dm.lin = user->variant.has_linear;
+    dv.cps = mp.cps; dv.cpv = mp.cpv;
+    dv.cpnsg = (mp.cpv && plan.emode == 5) ? plan.g5.NSG : 0;
+    return VA_OK;
+}
+
+// Step 3: Dims and the rest of Dev that follow from the descriptor and the plan
+int fill_dims(va_handle h, const va_problem_desc *d, const EvalPlan &plan)
+{
+    Dev &dv = h->dv;
+    Dims &dm = dv.dm;
+    const bool tdp = d->p_time_dependent != 0;
+    dm.D = d->D; dm.N = d->N_model; dm.ND = dm.D * dm.N; dm.L = d->L; dm.N_data = d->N_data;
+    dm.nskip = d->merr_nskip; dm.NP = d->NP; dm.NPest = d->NPest; dm.B = d->batch;
+    dm.disc = d->disc;
+    dm.tdp = tdp ? 1 : 0; dm.NPt = d->NP; dm.NPe = d->NPest;
+    dm.bounded = (d->lower && d->upper) ? 1 : 0;
+    if (tdp) { dm.ND = dm.N * (dm.D + dm.NPe); dm.NP = 0; dm.NPest = 0; }   // one flat run for the L-BFGS kernels
+    set_ld(dm);
+    dm.emode = plan.emode; dm.RY = plan.RY; dm.NT = plan.NT; dm.maxr = plan.maxr; dm.T = plan.T; dm.ntiles = plan.ntiles;
+    dm.ghost = plan.ghost;
+    dv.g4 = plan.g4; dv.g5 = plan.g5;
+    if (dm.emode == 4 && (unsigned long long)dm.B * dm.ntiles * dm.ntiles >= (1ull << 32))      // (umulhi by ntiles_magic would no longer be an exact division)
+        return fail(VA_EUNSUPPORTED, "batch x tiles too large for the wave-private kernel: pass eval_kernel=3");
+    dv.ntiles_magic = (unsigned)(((1ull << 32) + dm.ntiles - 1) / dm.ntiles);
+    // fold the tail into the evaluation kernel while the whole grid is resident at once (<= 8 workgroups per CU)
+    h->fold = (long)dm.B * dm.ntiles <= 8L * 256;
+    dm.nprow = dm.ntiles;                                                    // one partial row per workgroup
+    dm.dt = d->dt_model;
+    dm.cme = d->L > 0 ? 1.0 / ((double)dm.L * dm.N_data) : 0.0;
+    dm.cfe = 1.0 / ((double)dm.D * (dm.N - 1));
+    dm.rm = d->rm; dm.rf0 = d->rf0;
+    const int npcols = dv.cpv ? dv.cps : d->NP;          // (column-parameter form: the shared scalars only)
+    dv.evcols = EP_GP + npcols <= 8 ? 8 : (EP_GP + npcols <= 16 ? 16 : 32);
+    // write-through gradient stores pay where the grid is one resident round and the end-of-kernel write-back
+    // of 10 MB is on the critical path (C3: -1.3 us); on large grids they cost 10 % (4096 seeds: 446 vs 404 us)
+    dv.gaux = h->fold ? 1 : 0;
+    dv.prio = 1;
+    return VA_OK;
+}
+
+// Step 4: does the tile fit the LDS, and the kernels' opt-in to more than 64 KiB of it (per kernel AND per device: once per handle)
+int prepare_kernels(va_handle h)
+{
+    Dev &dv = h->dv;
+    const Dims &dm = dv.dm;
+    // the flat kernel keeps 3 staged arrays of (T + halo) rows: up to the CU's 160 KiB
+    size_t need = eval_lds_bytes(dv);
+    if (dm.emode == 5) { dv.lsrun = 1; need = std::max(need, eval_lds_bytes(dv)); dv.lsrun = 0; }
+    const size_t cap = 160 * 1024;
+    if (need > cap)
+        return fail(VA_EUNSUPPORTED, "a tile of %d rows x D=%d needs %zu B of LDS (> %zu): state too wide for this kernel",
+                    dm.T, dm.D, need, cap);
+    hipError_t e = h->user_prepare ? (hipError_t)h->user_prepare(&dv) : prepare_eval(dv, h->rhs);
+    if (e == hipSuccess && dm.bounded) e = prepare_lbfgsb(dv);
+    if (e != hipSuccess) return fail(VA_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
+    return VA_OK;
+}
+
+// The problem data of an ODE handle between its allocation and its upload: the device buffers, and the host images the
+// uploads read.  The uploads are asynchronous copies from this pageable memory, so ONE of these lives in the frame of
+// va_problem_create, declared before the first step that fills it, and must not be destroyed, resized or refilled until
+// finish_create has synchronised the stream.  It is declared BEFORE the HandleOwner: destruction order is part of the rule,
+// since on a failing return it is the owner's va_problem_destroy that synchronises the stream, and that must happen while
+// these vectors still exist.  (No helper keeps a staging vector of its own.)
+struct OdeData {
+    std::vector<double> Ys, rms, rf_fill, lo, hi;
+    std::vector<int> lmap, colp_map;
+    size_t LY = 0, np_seed = 0, rm_elems = 0;
+    bool warr5 = false;        // k_eval5 streams both weight images: scalar weights are spread out into arrays
+    int *lmap_d = nullptr, *pidx_d = nullptr, *ystrip_d = nullptr, *lidx_d = nullptr;
+    double *Y_d = nullptr, *rm_d = nullptr, *rf_d = nullptr, *P_d = nullptr, *t_d = nullptr, *st_d = nullptr, *lo_d = nullptr, *hi_d = nullptr;
+};
+
+// Step 5a: the device buffers of the problem data (zero-filled on the stream, ahead of the uploads into them)
+int alloc_problem_data(va_handle h, const va_problem_desc *d, const EvalPlan &plan, OdeData &o)
+{
+    Dev &dv = h->dv;
+    Dims &dm = dv.dm;
+    const size_t B = dm.B;
+    TRY(h->alloc(&o.lmap_d, dm.D));
+    // (two rows + a line of padding: the streaming kernel stages observation rows by whole 16-byte pieces, two rows at a time)
+    const size_t LY = dm.emode == 5 ? (size_t)dv.g5.LY : (size_t)dm.L;        // row pitch of Y (and of the RM image of k_eval5) on the device
+    o.LY = LY;
+    TRY(h->alloc(&o.Y_d, (size_t)dm.N_data * LY + 4 * LY + 16));   // (k_eval5 stages row pairs: one pair before the first row, one past the last)
+    o.Y_d += 2 * (LY / 2) + (LY & 1) * 2;                   // an even number of doubles >= L: the data keep their 16-byte alignment
+    if (dm.emode == 5) TRY(h->alloc(&o.ystrip_d, plan.ystrip.size()));
+    o.np_seed = dm.tdp ? (size_t)dm.N * dm.NPt : (size_t)dm.NPt;       // parameters stored per seed
+    TRY(h->alloc(&o.pidx_d, dm.NPe));
+    TRY(h->alloc(&o.P_d, B * o.np_seed));
+    o.rm_elems = (size_t)dm.N_data * dm.L * (d->rm_kind == 2 ? dm.L : 1);
+    o.warr5 = dm.emode == 5 && dv.g5.warr;
+    if (o.warr5) {
+        // (as Y: one row pair in front and behind; L is even on this path)
+        TRY(h->alloc(&o.rm_d, (size_t)dm.N_data * LY + 4 * LY + 16));
+        o.rm_d += LY;
+    } else if (d->rm_kind) TRY(h->alloc(&o.rm_d, o.rm_elems));
+    if (d->rm_kind == 2) TRY(h->alloc(&o.lidx_d, dm.L));
+    if (o.warr5) {
+        TRY(h->alloc(&o.rf_d, (size_t)(dm.N + 3) * dm.D + 16));
+        o.rf_d += dm.D;
+    } else if (d->rf_kind) TRY(h->alloc(&o.rf_d, (size_t)(dm.N - 1) * dm.D * (d->rf_kind == 2 ? dm.D : 1)));
+    if (dm.bounded) {
+        const int nv = dm.ND + dm.NPest;
+        o.lo.assign(dm.ld, -HUGE_VAL); o.hi.assign(dm.ld, HUGE_VAL);
+        for (int i = 0; i < nv; ++i) { o.lo[i] = d->lower[i]; o.hi[i] = d->upper[i]; }
+        bool boxed = true;
+        for (int i = 0; i < nv; ++i) boxed = boxed && o.lo[i] > -HUGE_VAL && o.hi[i] < HUGE_VAL;
+        if (boxed) dm.bounded |= 2;
+        TRY(h->alloc(&o.lo_d, (size_t)dm.ld)); TRY(h->alloc(&o.hi_d, (size_t)dm.ld));
+    }
+    if (d->t_model) TRY(h->alloc(&o.t_d, (size_t)dm.N));
+    if (d->n_stim > 0) TRY(h->alloc(&o.st_d, (size_t)dm.N * d->n_stim));
+    return VA_OK;
+}
+
+// Step 5b: stage the problem data in o and upload it.
+// On the device Lidx is ascending: data column l pairs with state column Lidx[l] in any order
+// (va_ode.py:141), so sorting Lidx and permuting the columns of Y (and of a weight array) the same
+// way changes nothing, and the kernels of narrow states find a column's data by counting the
+// observed columns below it (obsmask) instead of loading a map.
+int upload_problem_data(va_handle h, const va_problem_desc *d, const UserRhs *user, const EvalPlan &plan, OdeData &o)
+{
+    Dev &dv = h->dv;
+    Dims &dm = dv.dm;
+    const size_t B = dm.B, LY = o.LY;
+    std::vector<int> perm(dm.L), lidx_sorted(dm.L);
+    for (int l = 0; l < dm.L; ++l) perm[l] = l;
+    if (d->rm_kind != 2) std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return d->Lidx[a] < d->Lidx[b]; });
+    for (int l = 0; l < dm.L; ++l) lidx_sorted[l] = d->Lidx[perm[l]];
+    o.Ys.assign((size_t)dm.N_data * LY, 0.0);
+    for (int n = 0; n < dm.N_data; ++n)
+        for (int l = 0; l < dm.L; ++l) o.Ys[(size_t)n * LY + l] = d->Y[(size_t)n * dm.L + perm[l]];
+    if (o.warr5 && d->rm_kind == 0) o.rms.assign((size_t)dm.N_data * LY, d->rm);
+    if (d->rm_kind == 1) {
+        o.rms.assign((size_t)dm.N_data * LY, 0.0);
+        for (int n = 0; n < dm.N_data; ++n)
+            for (int l = 0; l < dm.L; ++l) o.rms[(size_t)n * LY + l] = d->rm_array[(size_t)n * dm.L + perm[l]];
+    }
+    o.lmap.assign(dm.D, -1);
+    for (int l = 0; l < dm.L; ++l) o.lmap[lidx_sorted[l]] = l;
+    dm.obsmask = 0ull;
+    if (dm.D <= 64) for (int l = 0; l < dm.L; ++l) dm.obsmask |= 1ull << lidx_sorted[l];
+    TRY(UPLOAD(o.lmap_d, o.lmap.data(), dm.D));
+    if (dm.emode == 5) { TRY(UPLOAD(o.ystrip_d, plan.ystrip.data(), plan.ystrip.size())); dv.ystrip = o.ystrip_d; }
+    TRY(UPLOAD(o.Y_d, o.Ys.data(), (size_t)dm.N_data * LY));
+    if (dm.NPe) TRY(UPLOAD(o.pidx_d, d->Pidx, dm.NPe));
+    TRY(UPLOAD(o.P_d, d->P, B * o.np_seed));
+    if (d->rm_kind || o.warr5) TRY(UPLOAD(o.rm_d, d->rm_kind != 2 ? o.rms.data() : d->rm_array, d->rm_kind != 2 ? o.rms.size() : o.rm_elems));
+    if (d->rm_kind == 2) TRY(UPLOAD(o.lidx_d, d->Lidx, dm.L));
+    if (o.warr5 && d->rf_kind == 0) o.rf_fill.assign((size_t)(dm.N - 1) * dm.D, d->rf0);
+    if (d->rf_kind || o.warr5) TRY(UPLOAD(o.rf_d, d->rf_kind ? d->rf0_array : o.rf_fill.data(), (size_t)(dm.N - 1) * dm.D * (d->rf_kind == 2 ? dm.D : 1)));
+    if (dm.bounded) { TRY(UPLOAD(o.lo_d, o.lo.data(), (size_t)dm.ld)); TRY(UPLOAD(o.hi_d, o.hi.data(), (size_t)dm.ld)); }
+    dv.pp.lo = o.lo_d; dv.pp.hi = o.hi_d;
+    if (d->t_model) TRY(UPLOAD(o.t_d, d->t_model, (size_t)dm.N));
+    if (d->n_stim > 0) TRY(UPLOAD(o.st_d, d->stim, (size_t)dm.N * d->n_stim));
+    dv.pp.lmap = o.lmap_d; dv.pp.Y = o.Y_d; dv.pp.rf0_arr = (d->rf_kind == 1 || o.warr5) ? o.rf_d : nullptr;
+    dv.pp.rf0_full = d->rf_kind == 2 ? o.rf_d : nullptr;
+    dv.pp.rm_arr = (d->rm_kind == 1 || o.warr5) ? o.rm_d : nullptr;
+    dv.pp.rm_full = d->rm_kind == 2 ? o.rm_d : nullptr; dv.pp.Lidx = o.lidx_d;
+    dv.pp.Pidx = o.pidx_d; dv.pp.Pfull = o.P_d;
+    if (dv.cpv) {
+        // column-parameter form: each shared scalar / vector entry -> its global index, then its index in p_est or -1
+        const int NT = dv.cps + dv.cpv;
+        std::vector<int> pest(d->NP, -1);
+        o.colp_map.assign(2 * (size_t)NT, 0);
+        for (int k = 0; k < d->NPest; ++k) pest[d->Pidx[k]] = k;
+        for (int j = 0; j < NT; ++j) { o.colp_map[j] = user->colp[2 + j]; o.colp_map[NT + j] = pest[o.colp_map[j]]; }
+        int *cm_d = nullptr;
+        TRY(h->alloc(&cm_d, o.colp_map.size()));
+        TRY(UPLOAD(cm_d, o.colp_map.data(), o.colp_map.size()));
+        dv.cpmap = cm_d;
+    }
+    dv.pp.tmodel = o.t_d; dv.pp.stim = o.st_d; dv.pp.nstim = d->n_stim;
+    return VA_OK;
+}
+
+// Step 6: few seeds, short paths: can the whole minimisation live in LDS?  (flat tile phases: any right-hand side, any
+// discretisation, weight arrays, merr_nskip, full weight matrices; not bounds, time-dependent parameters, a dense
+// linear part, more than RHS_MAX_NP parameters, or the padded observation rows of the streaming kernel)
+int choose_persist(va_handle h, const va_problem_desc *d, const UserRhs *user)
+{
+    Dev &dv = h->dv;
+    const Dims &dm = dv.dm;
+    const size_t B = dm.B;
+    if (dm.bounded || dm.tdp || dm.lin || d->NP > RHS_MAX_NP || dm.emode == 5 || (user && !user->seed_kernel)) return VA_OK;
+    int G = 0, T = 0, ncu = 0;
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d->device));
+    h->pz_maxG = ncu / (int)B;
+    if (h->pz_maxG < 1 || !persist_geometry(dm.N, dm.D, dm.L, dm.NP, dm.NPest, dm.m, dm.disc, PZ_LDS_BYTES, h->pz_maxG, 0, &G, &T)) return VA_OK;
+    Dev dvp = dv;
+    dvp.dm.T = T; dvp.dm.ntiles = G;
+    const hipError_t e = h->user_seed ? (hipError_t)h->user_seed(&dvp, 0, nullptr) : seed_kernel_builtin(dvp, false, nullptr);
+    if (e != hipSuccess) { (void)hipGetLastError(); return VA_OK; }
+    h->persist = true; h->pz_G = G; h->pz_T = T;
+    // (sized for the most workgroups a seed may get: va_problem_tune may choose other slices)
+    const size_t units = B * 2 * (size_t)h->pz_maxG * (size_t)pz_row_granules(dm.D) * 2;     // 8-byte units: 16 per granule pair
+    TRY(h->alloc(&dv.pz.xch, units));
+    h->pz_xch_bytes = units * 8;
+    unsigned long long *misc = nullptr;
+    TRY(h->alloc(&misc, 2 + PZ_NSTAMP));
+    h->pz_misc = misc;
+    dv.pz.abort_flag = (int *)misc; dv.pz.cycles = misc + 1; dv.pz.stamps = (double *)(misc + 2);
+    return VA_OK;
+}
+
+// CUs of a device, or 256 where it cannot be asked (a device that does not exist is refused by begin_create, after the
+// descriptor's own checks)
+int cu_count(int device)
+{
+    int ncu = 256;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void)hipGetLastError(); ncu = 256; }
+    return ncu;
+}
+
+// Dims and NnetDev of a network handle, from the descriptor and its plan
+void fill_nnet_dims(va_handle h, const va_nnet_desc *d, const NnetPlan &p)
+{
+    Dev &dv = h->dv;
+    NnetDev &nn = h->nn;
+    memset(&nn, 0, sizeof nn);
+    Dims &dm = dv.dm;
+    // to the L-BFGS kernels the unknown vector is one flat run of ND doubles with no tail
+    dm.D = p.NDnet; dm.N = d->M; dm.ND = (int)p.nvar; dm.NP = 0; dm.NPest = 0; dm.B = d->batch;
+    dm.L = d->L_in + d->L_out; dm.N_data = d->M; dm.nskip = 1; dm.disc = VA_DISC_FORWARDMAP;
+    set_ld(dm);
+    dm.cme = 1.0 / ((double)(d->L_in + d->L_out) * d->M);                 /* va_nnet.py:173 */
+    dm.cfe = d->rf0 / ((double)(p.NDnet - p.s[0]) * d->M);                /* va_nnet.py:255 */
+    dm.rm = d->rm_in; dm.rf0 = d->rf0;
+    dv.evcols = 8;                 // the network kernels fill EP_ME .. EP_GMAX only
+    dm.nprow = p.nprow;
+    dm.ntiles = dm.nprow; dm.T = NN_TILE; dm.emode = 0;
+
+    nn.NL = d->n_layers; nn.M = d->M; nn.NDnet = p.NDnet; nn.NDens = p.NDnet * d->M; nn.NP = d->NP; nn.NPest = d->NPest;
+    nn.act = d->activation; nn.Lin = d->L_in; nn.Lout = d->L_out; nn.rm_in = d->rm_in; nn.rm_out = d->rm_out;
+    nn.mch = p.mch; nn.nmch = p.nmch;
+    nn.n0 = p.n0; nn.n1 = p.n1; nn.n2 = p.n2; nn.n3 = p.n3; nn.n4 = p.n4; nn.nraw = p.nraw;
+    nn.small = p.small;
+    nn.nfb = p.nfb; nn.wfsz = p.wfsz; nn.fb_slots = p.fb_slots; nn.fused = p.fused;
+}
+
+// The device image of a network: its buffers, then the solver state, then the uploads.  The uploads read the plan's
+// vectors and the caller's arrays: p lives in the frame of va_nnet_problem_create until finish_create has synchronised.
+int create_nnet_image(va_handle h, const va_nnet_desc *d, const NnetPlan &p)
+{
+    Dev &dv = h->dv;
+    NnetDev &nn = h->nn;
+    const Dims &dm = dv.dm;
+    const int NL = d->n_layers;
+    const size_t B = dm.B;
+    int *s_d = nullptr, *off_d = nullptr, *woff_d = nullptr, *boff_d = nullptr, *lin_d = nullptr, *lout_d = nullptr, *pmap_d = nullptr;
+    double *din_d = nullptr, *dout_d = nullptr, *P_d = nullptr;
+    NnetTile *t1_d = nullptr, *t2_d = nullptr, *t3_d = nullptr;
+    TRY(h->alloc(&s_d, NL)); TRY(h->alloc(&off_d, NL + 1)); TRY(h->alloc(&woff_d, NL - 1)); TRY(h->alloc(&boff_d, NL - 1));
+    TRY(h->alloc(&lin_d, p.s[0])); TRY(h->alloc(&lout_d, p.s[NL - 1])); TRY(h->alloc(&pmap_d, d->NP));
+    TRY(h->alloc(&din_d, (size_t)d->M * d->L_in)); TRY(h->alloc(&dout_d, (size_t)d->M * d->L_out));
+    TRY(h->alloc(&P_d, B * d->NP)); TRY(h->alloc(&nn.Pw, B * d->NP));
+    TRY(h->alloc(&nn.delta, B * dm.ld));
+    TRY(h->alloc(&nn.Xw, B * dm.ld));
+    if (p.fold_rows) TRY(h->alloc(&nn.raw, B * nn.nraw * EP_GP));
+    TRY(h->alloc(&nn.gpart, B * nn.nmch * (size_t)d->NP));
+    int *wfoff_d = nullptr;
+    if (p.fb_ok) {
+        TRY(h->alloc(&nn.Wf, B * (size_t)nn.wfsz));
+        TRY(h->alloc(&wfoff_d, 2 * (NL - 1)));
+        TRY(h->alloc(&dv.pz.stamps, (size_t)PZ_NSTAMP));       // (measurement builds of k_nnet_fb: va_measure.h)
+        TRY(h->alloc(&nn.fb_cu, (size_t)16));
+    }
+    TRY(h->alloc(&t1_d, p.t1.size())); TRY(h->alloc(&t2_d, p.t2.size())); TRY(h->alloc(&t3_d, p.t3.size()));
+    TRY(alloc_solver_state(h));
+    TRY(UPLOAD(s_d, p.s.data(), NL)); TRY(UPLOAD(off_d, p.off.data(), NL + 1));
+    TRY(UPLOAD(woff_d, p.woff.data(), NL - 1)); TRY(UPLOAD(boff_d, p.boff.data(), NL - 1));
+    TRY(UPLOAD(lin_d, p.lin.data(), p.s[0])); TRY(UPLOAD(lout_d, p.lout.data(), p.s[NL - 1])); TRY(UPLOAD(pmap_d, p.pmap.data(), d->NP));
+    if (d->L_in) TRY(UPLOAD(din_d, d->data_in, (size_t)d->M * d->L_in));
+    if (d->L_out) TRY(UPLOAD(dout_d, d->data_out, (size_t)d->M * d->L_out));
+    TRY(UPLOAD(P_d, d->P, B * d->NP));
+    if (p.fb_ok) { TRY(UPLOAD(wfoff_d, p.wfoff.data(), 2 * (NL - 1))); nn.wfoff = wfoff_d; }
+    TRY(UPLOAD(t1_d, p.t1.data(), p.t1.size())); TRY(UPLOAD(t2_d, p.t2.data(), p.t2.size()));
+    if (!p.t3.empty()) TRY(UPLOAD(t3_d, p.t3.data(), p.t3.size()));
+    nn.s = s_d; nn.off = off_d; nn.woff = woff_d; nn.boff = boff_d; nn.lmap_in = lin_d; nn.lmap_out = lout_d;
+    nn.pmap = pmap_d; nn.din = din_d; nn.dout = dout_d; nn.Pfix = P_d; nn.t1 = t1_d; nn.t2 = t2_d; nn.t3 = t3_d;
+    if (d->rm_in_matrix) {
+        // full measurement matrices (va_nnet.py:136-139): the kernels walk the layer's observed neurons
+        double *ri = nullptr, *ro = nullptr; int *li = nullptr, *lo = nullptr;
+        TRY(h->alloc(&ri, (size_t)d->L_in * d->L_in + 1)); TRY(h->alloc(&ro, (size_t)d->L_out * d->L_out + 1));
+        TRY(h->alloc(&li, d->L_in + 1)); TRY(h->alloc(&lo, d->L_out + 1));
+        if (d->L_in) { TRY(UPLOAD(ri, d->rm_in_matrix, (size_t)d->L_in * d->L_in)); TRY(UPLOAD(li, d->Lidx_in, d->L_in)); }
+        if (d->L_out) { TRY(UPLOAD(ro, d->rm_out_matrix, (size_t)d->L_out * d->L_out)); TRY(UPLOAD(lo, d->Lidx_out, d->L_out)); }
+        nn.rmm_in = ri; nn.rmm_out = ro; nn.lidx_in = li; nn.lidx_out = lo;
+    }
+    if (p.fb_ok) {
+        const hipError_t e = prepare_nnet_fb(nn, h->user_act);
+        if (e != hipSuccess) { (void)hipGetLastError(); nn.Wf = nullptr; }      // (the tune knob then refuses)
+    }
     return VA_OK;
 }
 
@@ -551,281 +1015,24 @@ int va_problem_create(const va_problem_desc *d, va_handle *out)
 {
     if (!d || !out) return fail(VA_EINVAL, "null argument");
     *out = nullptr;
-    if (d->struct_size != (int32_t)sizeof(va_problem_desc)) return fail(VA_EINVAL, "struct_size %d != %zu", d->struct_size, sizeof(va_problem_desc));
-    if (d->batch < 1 || d->D < 1 || d->N_model < 2 || d->N_data < 1 || d->L < 0 || d->merr_nskip < 1)
-        return fail(VA_EINVAL, "bad sizes (batch=%d D=%d N_model=%d N_data=%d L=%d nskip=%d)", d->batch, d->D, d->N_model, d->N_data, d->L, d->merr_nskip);
-    if ((int64_t)(d->N_data - 1) * d->merr_nskip + 1 != d->N_model)      /* va_ode.py:557 */
-        return fail(VA_EINVAL, "N_model (%d) must equal (N_data-1)*merr_nskip+1 (%lld)", d->N_model,
-                    (long long)(d->N_data - 1) * d->merr_nskip + 1);
-    if (d->disc < VA_DISC_EULER || d->disc > VA_DISC_FORWARDMAP) return fail(VA_EINVAL, "unknown disc %d", d->disc);
-    if (d->disc == VA_DISC_SIMPSON_HERMITE && (d->N_model % 2) == 0)
-        return fail(VA_EINVAL, "SimpsonHermite needs an odd number of time points (N_model=%d)", d->N_model);
     UserRhs user_copy;
     const UserRhs *user = nullptr;
-    if (d->rhs >= VA_RHS_USER_BASE) {
-        std::lock_guard<std::mutex> lock(g_user_rhs_mutex);
-        if ((size_t)(d->rhs - VA_RHS_USER_BASE) >= g_user_rhs.size()) return fail(VA_EINVAL, "rhs module id %d was never registered", d->rhs);
-        user_copy = g_user_rhs[d->rhs - VA_RHS_USER_BASE];      // (the vector may grow under another thread)
-        user = &user_copy;
-        if (user->NP != d->NP || user->D != d->D || user->NSTIM != d->n_stim)
-            return fail(VA_EINVAL, "rhs module %s was generated for D=%d NP=%d n_stim=%d, problem has D=%d NP=%d n_stim=%d",
-                        user->path.c_str(), user->D, user->NP, user->NSTIM, d->D, d->NP, d->n_stim);
-    } else if (d->rhs != VA_RHS_LORENZ96) return fail(VA_EUNSUPPORTED, "unknown built-in rhs %d", d->rhs);
-    if (d->rhs == VA_RHS_LORENZ96 && (d->NP != RhsL96::NP || d->D < 4))
-        return fail(VA_EINVAL, "Lorenz-96 needs NP=1 and D>=4 (NP=%d D=%d)", d->NP, d->D);
-    if (d->n_stim < 0 || (d->n_stim > 0 && !d->stim)) return fail(VA_EINVAL, "n_stim=%d without a stimulus array", d->n_stim);
-    // (more than RHS_BIG_NP parameters: a module in column-parameter form only, on k_eval4 / k_eval5 -- checked below)
-    const bool noflat = d->NP > RHS_BIG_NP;
-    if (noflat && !(user && !user->colp.empty()))
-        return fail(VA_EUNSUPPORTED, "NP=%d > %d: only a generated module in column-parameter form (shared scalars + per-column "
-                                     "vectors) carries more, and this model has none", d->NP, RHS_BIG_NP);
-    if (d->NPest < 0 || d->NPest > d->NP) return fail(VA_EINVAL, "bad NP/NPest (%d/%d)", d->NP, d->NPest);
-    const bool tdp = d->p_time_dependent != 0;
-    // more than RHS_MAX_NP parameters: the flat kernel carries them (their gradient partials in a table of their own)
-    const bool bigp = d->NP > RHS_MAX_NP;
-    if (bigp && tdp) return fail(VA_EUNSUPPORTED, "time-dependent parameters: at most %d of them", RHS_MAX_NP);
-    if (tdp && d->disc != VA_DISC_TRAPEZOID && d->disc != VA_DISC_SIMPSON_HERMITE)
-        return fail(VA_EUNSUPPORTED, "time-dependent parameters: trapezoid and SimpsonHermite only (upstream's euler/forwardmap "
-                                     "branches are inconsistent, va_ode.py:345-349)");
-    if (tdp && (int64_t)d->N_model * (d->D + d->NPest) > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_var does not fit 32-bit indexing");
-    if (!d->Y || (d->L > 0 && !d->Lidx) || !d->P || (d->NPest > 0 && !d->Pidx)) return fail(VA_EINVAL, "null array in desc");
-    if ((d->rm_kind && !d->rm_array) || (d->rf_kind && !d->rf0_array)) return fail(VA_EINVAL, "rm/rf array kind without array");
-    if ((d->lower != nullptr) != (d->upper != nullptr)) return fail(VA_EINVAL, "lower and upper bounds come together");
-    {
-        std::vector<char> seen(d->D, 0);
-        for (int l = 0; l < d->L; ++l) {
-            if (d->Lidx[l] < 0 || d->Lidx[l] >= d->D) return fail(VA_EINVAL, "Lidx[%d]=%d outside [0,D)", l, d->Lidx[l]);
-            // any order is fine (data column l pairs with state column Lidx[l], va_ode.py:141); a state
-            // column observed twice has no slot in the column -> data-column map the kernels use
-            if (seen[d->Lidx[l]] && d->rm_kind != 2) return fail(VA_EUNSUPPORTED, "Lidx lists state column %d twice", d->Lidx[l]);
-            seen[d->Lidx[l]] = 1;
-        }
-    }
-    for (int k = 0; k < d->NPest; ++k)
-        if (d->Pidx[k] < 0 || d->Pidx[k] >= d->NP) return fail(VA_EINVAL, "Pidx[%d]=%d outside [0,NP)", k, d->Pidx[k]);
-    const int m = d->lbfgs_m > 0 ? d->lbfgs_m : 10;
-    if (m > MAX_M) return fail(VA_EINVAL, "lbfgs_m=%d > %d", m, MAX_M);
-    const int max_beta = d->max_beta > 0 ? d->max_beta : 1;
-
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (d->device < 0 || d->device >= ndev) return fail(VA_EINVAL, "device %d of %d", d->device, ndev);
-    HIPCHK(hipSetDevice(d->device));
-
-    va_handle h = new va_problem_s();
-    h->device = d->device; h->rhs = d->rhs; h->keep_paths = d->keep_paths;
-    h->user_launch = user ? user->launch : nullptr;
-    h->user_prepare = user ? user->prepare : nullptr;
-    h->user_seed = user ? user->seed_kernel : nullptr;
-    if (d->stream) h->stream = (hipStream_t)d->stream;
-    else {
-        hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete h; return fail(VA_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-        h->own_stream = true;
-    }
-    Dev &dv = h->dv;
-    memset(&dv, 0, sizeof dv);
-    Dims &dm = dv.dm;
-    dm.D = d->D; dm.N = d->N_model; dm.ND = dm.D * dm.N; dm.L = d->L; dm.N_data = d->N_data;
-    dm.nskip = d->merr_nskip; dm.NP = d->NP; dm.NPest = d->NPest; dm.B = d->batch; dm.m = m;
-    dm.disc = d->disc;
-    dm.tdp = tdp ? 1 : 0; dm.NPt = d->NP; dm.NPe = d->NPest;
-    dm.bounded = (d->lower && d->upper) ? 1 : 0;
-    if (tdp) { dm.ND = dm.N * (dm.D + dm.NPe); dm.NP = 0; dm.NPest = 0; }   // one flat run for the L-BFGS kernels
-    dm.ld = ((dm.ND + dm.NPest + 15) / 16) * 16;
-    EvalPlan plan;
-    if (!user) {
-        EvalForm l96;
-        l96.ne = RhsL96s::NE; l96.ghost = RhsL96g::GHOST; l96.has_reach5 = true;
-        l96.reach5[0] = t5_xl<RhsL96s>(); l96.reach5[1] = t5_xr<RhsL96s>(); l96.reach5[2] = t5_gl<RhsL96s>(); l96.reach5[3] = t5_gr<RhsL96s>();
-        plan = plan_eval(d, l96);
-    }
-    else {
-        ModulePlan mp;
-        if (int rc = plan_module(d, *user, mp)) { va_problem_destroy(h); return rc; }
-        plan = mp.plan;
-        dm.lin = user->variant.has_linear;
-        if (mp.variant) { h->user_launch = user->launch_var; h->user_prepare = user->prepare_var; }
-        dv.cps = mp.cps; dv.cpv = mp.cpv;
-        dv.cpnsg = (mp.cpv && plan.emode == 5) ? plan.g5.NSG : 0;
-    }
-    dm.emode = plan.emode; dm.RY = plan.RY; dm.NT = plan.NT; dm.maxr = plan.maxr; dm.T = plan.T; dm.ntiles = plan.ntiles;
-    dm.ghost = plan.ghost;
-    dv.g4 = plan.g4; dv.g5 = plan.g5;
-    const std::vector<int> &ystrip_h = plan.ystrip;
-    if (dm.emode == 4 && (unsigned long long)dm.B * dm.ntiles * dm.ntiles >= (1ull << 32)) {
-        va_problem_destroy(h);        // (umulhi by ntiles_magic would no longer be an exact division)
-        return fail(VA_EUNSUPPORTED, "batch x tiles too large for the wave-private kernel: pass eval_kernel=3");
-    }
-    dv.ntiles_magic = (unsigned)(((1ull << 32) + dm.ntiles - 1) / dm.ntiles);
-    // fold the tail into the evaluation kernel while the whole grid is resident at once (<= 8 workgroups per CU)
-    h->fold = (long)dm.B * dm.ntiles <= 8L * 256;
-    dm.nprow = dm.ntiles;                                                    // one partial row per workgroup
-    dm.chunk = VEC_CHUNK; dm.nchunks = (dm.ld + VEC_CHUNK - 1) / VEC_CHUNK;
-    dm.dt = d->dt_model;
-    dm.cme = d->L > 0 ? 1.0 / ((double)dm.L * dm.N_data) : 0.0;
-    dm.cfe = 1.0 / ((double)dm.D * (dm.N - 1));
-    dm.rm = d->rm; dm.rf0 = d->rf0;
-    dv.ups = UP_OLD + 4 * m; dv.max_beta = max_beta; dv.nbeta = 1;
-    const int npcols = dv.cpv ? dv.cps : d->NP;          // (column-parameter form: the shared scalars only)
-    dv.evcols = EP_GP + npcols <= 8 ? 8 : (EP_GP + npcols <= 16 ? 16 : 32);
-    // write-through gradient stores pay where the grid is one resident round and the end-of-kernel write-back
-    // of 10 MB is on the critical path (C3: -1.3 us); on large grids they cost 10 % (4096 seeds: 446 vs 404 us)
-    dv.gaux = h->fold ? 1 : 0;
-    dv.prio = 1;
-    dv.o.m = m; dv.o.maxiter = 15000; dv.o.maxls = 20; dv.o.maxfun = 15000; dv.o.ftol = 2.2204460492503131e-09; dv.o.gtol = 1e-5;
-
-    {
-        // the flat kernel keeps 3 staged arrays of (T + halo) rows: up to the CU's 160 KiB
-        size_t need = eval_lds_bytes(dv);
-        if (dm.emode == 5) { dv.lsrun = 1; need = std::max(need, eval_lds_bytes(dv)); dv.lsrun = 0; }
-        const size_t cap = 160 * 1024;
-        if (need > cap) {
-            const int T = dm.T, D = dm.D;
-            va_problem_destroy(h);
-            return fail(VA_EUNSUPPORTED, "a tile of %d rows x D=%d needs %zu B of LDS (> %zu): state too wide for this kernel",
-                        T, D, need, cap);
-        }
-        // more than 64 KiB of dynamic LDS is an opt-in per kernel AND per device: once per handle
-        hipError_t e = h->user_prepare ? (hipError_t)h->user_prepare(&dv) : prepare_eval(dv, h->rhs);
-        if (e == hipSuccess && dm.bounded) e = prepare_lbfgsb(dv);
-        if (e != hipSuccess) {
-            va_problem_destroy(h);
-            return fail(VA_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
-        }
-    }
-
-    int rc = VA_OK;
-    const size_t B = dm.B;
-    int *lmap_d = nullptr, *pidx_d = nullptr;
-    double *Y_d = nullptr, *rm_d = nullptr, *rf_d = nullptr, *P_d = nullptr, *t_d = nullptr, *st_d = nullptr;
-#define TRY(x) do { rc = (x); if (rc) { va_problem_destroy(h); return rc; } } while (0)
-    TRY(h->alloc(&lmap_d, dm.D));
-    // (two rows + a line of padding: the streaming kernel stages observation rows by whole 16-byte pieces, two rows at a time)
-    const size_t LY = dm.emode == 5 ? (size_t)dv.g5.LY : (size_t)dm.L;        // row pitch of Y (and of the RM image of k_eval5) on the device
-    TRY(h->alloc(&Y_d, (size_t)dm.N_data * LY + 4 * LY + 16));   // (k_eval5 stages row pairs: one pair before the first row, one past the last)
-    Y_d += 2 * (LY / 2) + (LY & 1) * 2;                   // an even number of doubles >= L: the data keep their 16-byte alignment
-    int *ystrip_d = nullptr;
-    if (dm.emode == 5) TRY(h->alloc(&ystrip_d, ystrip_h.size()));
-    const size_t np_seed = tdp ? (size_t)dm.N * dm.NPt : (size_t)dm.NPt;       // parameters stored per seed
-    TRY(h->alloc(&pidx_d, dm.NPe));
-    TRY(h->alloc(&P_d, B * np_seed));
-    if (d->rm_kind < 0 || d->rm_kind > 2) { va_problem_destroy(h); return fail(VA_EINVAL, "rm_kind %d", d->rm_kind); }
-    const size_t rm_elems = (size_t)dm.N_data * dm.L * (d->rm_kind == 2 ? dm.L : 1);
-    int *lidx_d = nullptr;
-    const bool warr5 = dm.emode == 5 && dv.g5.warr;      // k_eval5 streams both weight images: scalar weights are spread out into arrays
-    if (warr5) {
-        // (as Y: one row pair in front and behind; L is even on this path)
-        TRY(h->alloc(&rm_d, (size_t)dm.N_data * LY + 4 * LY + 16));
-        rm_d += LY;
-    } else if (d->rm_kind) TRY(h->alloc(&rm_d, rm_elems));
-    if (d->rm_kind == 2) TRY(h->alloc(&lidx_d, dm.L));
-    if (warr5) {
-        TRY(h->alloc(&rf_d, (size_t)(dm.N + 3) * dm.D + 16));
-        rf_d += dm.D;
-    } else if (d->rf_kind) TRY(h->alloc(&rf_d, (size_t)(dm.N - 1) * dm.D * (d->rf_kind == 2 ? dm.D : 1)));
-    double *lo_d = nullptr, *hi_d = nullptr;
-    std::vector<double> lo_h, hi_h;
-    if (dm.bounded) {
-        const int nv = dm.ND + dm.NPest;
-        lo_h.assign(dm.ld, -HUGE_VAL); hi_h.assign(dm.ld, HUGE_VAL);
-        for (int i = 0; i < nv; ++i) {
-            if (!(d->lower[i] <= d->upper[i])) { va_problem_destroy(h); return fail(VA_EINVAL, "lower[%d] > upper[%d] (or NaN)", i, i); }
-            lo_h[i] = d->lower[i]; hi_h[i] = d->upper[i];
-        }
-        bool boxed = true;
-        for (int i = 0; i < nv; ++i) boxed = boxed && lo_h[i] > -HUGE_VAL && hi_h[i] < HUGE_VAL;
-        if (boxed) { dm.bounded |= 2; dv.dm.bounded |= 2; }
-        TRY(h->alloc(&lo_d, (size_t)dm.ld)); TRY(h->alloc(&hi_d, (size_t)dm.ld));
-    }
-    if (d->t_model) TRY(h->alloc(&t_d, (size_t)dm.N));
-    if (d->n_stim > 0) TRY(h->alloc(&st_d, (size_t)dm.N * d->n_stim));
-    TRY(alloc_solver_state(h, max_beta, d->keep_paths));
-
-    // On the device Lidx is ascending: data column l pairs with state column Lidx[l] in any order
-    // (va_ode.py:141), so sorting Lidx and permuting the columns of Y (and of a weight array) the same
-    // way changes nothing, and the kernels of narrow states find a column's data by counting the
-    // observed columns below it (obsmask) instead of loading a map.
-    std::vector<int> perm(dm.L), lidx_sorted(dm.L);
-    for (int l = 0; l < dm.L; ++l) perm[l] = l;
-    if (d->rm_kind != 2) std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return d->Lidx[a] < d->Lidx[b]; });
-    for (int l = 0; l < dm.L; ++l) lidx_sorted[l] = d->Lidx[perm[l]];
-    std::vector<double> Ys((size_t)dm.N_data * LY, 0.0), rms;
-    for (int n = 0; n < dm.N_data; ++n)
-        for (int l = 0; l < dm.L; ++l) Ys[(size_t)n * LY + l] = d->Y[(size_t)n * dm.L + perm[l]];
-    if (warr5 && d->rm_kind == 0) rms.assign((size_t)dm.N_data * LY, d->rm);
-    if (d->rm_kind == 1) {
-        rms.assign((size_t)dm.N_data * LY, 0.0);
-        for (int n = 0; n < dm.N_data; ++n)
-            for (int l = 0; l < dm.L; ++l) rms[(size_t)n * LY + l] = d->rm_array[(size_t)n * dm.L + perm[l]];
-    }
-    std::vector<int> lmap(dm.D, -1);
-    for (int l = 0; l < dm.L; ++l) lmap[lidx_sorted[l]] = l;
-    dm.obsmask = 0ull;
-    if (dm.D <= 64) for (int l = 0; l < dm.L; ++l) dm.obsmask |= 1ull << lidx_sorted[l];
-    dv.dm.obsmask = dm.obsmask;
-#define H2D(dst, src, n, T) do { hipError_t e_ = hipMemcpyAsync(dst, src, sizeof(T) * (n), hipMemcpyHostToDevice, h->stream); \
-        if (e_ != hipSuccess) { va_problem_destroy(h); return fail(VA_EHIP, "H2D %s: %s", #dst, hipGetErrorString(e_)); } } while (0)
-    H2D(lmap_d, lmap.data(), dm.D, int);
-    if (dm.emode == 5) { H2D(ystrip_d, ystrip_h.data(), ystrip_h.size(), int); dv.ystrip = ystrip_d; }
-    H2D(Y_d, Ys.data(), (size_t)dm.N_data * LY, double);
-    if (dm.NPe) H2D(pidx_d, d->Pidx, dm.NPe, int);
-    H2D(P_d, d->P, B * np_seed, double);
-    if (d->rm_kind || warr5) H2D(rm_d, d->rm_kind != 2 ? rms.data() : d->rm_array, d->rm_kind != 2 ? rms.size() : rm_elems, double);
-    if (d->rm_kind == 2) H2D(lidx_d, d->Lidx, dm.L, int);
-    std::vector<double> rf_fill;
-    if (warr5 && d->rf_kind == 0) rf_fill.assign((size_t)(dm.N - 1) * dm.D, d->rf0);
-    if (d->rf_kind || warr5) H2D(rf_d, d->rf_kind ? d->rf0_array : rf_fill.data(), (size_t)(dm.N - 1) * dm.D * (d->rf_kind == 2 ? dm.D : 1), double);
-    if (dm.bounded) { H2D(lo_d, lo_h.data(), (size_t)dm.ld, double); H2D(hi_d, hi_h.data(), (size_t)dm.ld, double); }
-    dv.pp.lo = lo_d; dv.pp.hi = hi_d;
-    if (d->t_model) H2D(t_d, d->t_model, (size_t)dm.N, double);
-    if (d->n_stim > 0) H2D(st_d, d->stim, (size_t)dm.N * d->n_stim, double);
-    dv.pp.lmap = lmap_d; dv.pp.Y = Y_d; dv.pp.rf0_arr = (d->rf_kind == 1 || warr5) ? rf_d : nullptr;
-    dv.pp.rf0_full = d->rf_kind == 2 ? rf_d : nullptr;
-    dv.pp.rm_arr = (d->rm_kind == 1 || warr5) ? rm_d : nullptr;
-    dv.pp.rm_full = d->rm_kind == 2 ? rm_d : nullptr; dv.pp.Lidx = lidx_d;
-    dv.pp.Pidx = pidx_d; dv.pp.Pfull = P_d;
-    if (dv.cpv) {
-        // column-parameter form: each shared scalar / vector entry -> its global index, then its index in p_est or -1
-        const int NT = dv.cps + dv.cpv;
-        std::vector<int> pest(d->NP, -1), cm(2 * (size_t)NT);
-        for (int k = 0; k < d->NPest; ++k) pest[d->Pidx[k]] = k;
-        for (int j = 0; j < NT; ++j) { cm[j] = user->colp[2 + j]; cm[NT + j] = pest[cm[j]]; }
-        int *cm_d = nullptr;
-        TRY(h->alloc(&cm_d, cm.size()));
-        H2D(cm_d, cm.data(), cm.size(), int);
-        dv.cpmap = cm_d;
-    }
-    dv.pp.tmodel = t_d; dv.pp.stim = st_d; dv.pp.nstim = d->n_stim;
-
-    // few seeds, short paths: can the whole minimisation live in LDS?  (flat tile phases: any right-hand side, any
-    // discretisation, weight arrays, merr_nskip, full weight matrices; not bounds, time-dependent parameters, a dense
-    // linear part, or the padded observation rows of the streaming kernel)
-    if (!dm.bounded && !tdp && !dm.lin && !bigp && dm.emode != 5 && (!user || user->seed_kernel)) {
-        int G = 0, T = 0, ncu = 0;
-        HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d->device));
-        h->pz_maxG = ncu / (int)B;
-        if (h->pz_maxG >= 1 && persist_geometry(dm.N, dm.D, dm.L, dm.NP, dm.NPest, m, dm.disc, PZ_LDS_BYTES, h->pz_maxG, 0, &G, &T)) {
-            Dev dvp = dv;
-            dvp.dm.T = T; dvp.dm.ntiles = G;
-            const hipError_t e = h->user_seed ? (hipError_t)h->user_seed(&dvp, 0, nullptr) : seed_kernel_builtin(dvp, false, nullptr);
-            if (e == hipSuccess) {
-                h->persist = true; h->pz_G = G; h->pz_T = T;
-                // (sized for the most workgroups a seed may get: va_problem_tune may choose other slices)
-                const size_t units = B * 2 * (size_t)h->pz_maxG * (size_t)pz_row_granules(dm.D) * 2;     // 8-byte units: 16 per granule pair
-                TRY(h->alloc(&dv.pz.xch, units));
-                h->pz_xch_bytes = units * 8;
-                unsigned long long *misc = nullptr;
-                TRY(h->alloc(&misc, 2 + PZ_NSTAMP));
-                h->pz_misc = misc;
-                dv.pz.abort_flag = (int *)misc; dv.pz.cycles = misc + 1; dv.pz.stamps = (double *)(misc + 2);
-            } else (void)hipGetLastError();
-        }
-    }
-    TRY(finish_create(h));
-#undef TRY
-#undef H2D
-    *out = h;
+    TRY(validate_desc(d, user_copy, &user));
+    // declared AHEAD of the owner: locals die in reverse order, so on a failing return the owner's va_problem_destroy
+    // synchronises the stream while the memory the queued uploads read is still there
+    EvalPlan plan;       // (its observation strips are uploaded: it lives as long as the staging below)
+    OdeData data;        // device buffers and host staging: alive until finish_create has synchronised the stream
+    HandleOwner h;
+    TRY(begin_create(d->device, d->stream, d->lbfgs_m, d->max_beta, d->keep_paths, h));
+    TRY(plan_problem(h.get(), d, user, plan));
+    TRY(fill_dims(h.get(), d, plan));
+    TRY(prepare_kernels(h.get()));
+    TRY(alloc_problem_data(h.get(), d, plan, data));
+    TRY(alloc_solver_state(h.get()));         // (reads dv.cpv / dv.cps: after plan_problem)
+    TRY(upload_problem_data(h.get(), d, user, plan, data));
+    TRY(choose_persist(h.get(), d, user));
+    TRY(finish_create(h.get()));
+    *out = h.release();
     return VA_OK;
 }
 
@@ -842,229 +1049,17 @@ int va_nnet_problem_create(const va_nnet_desc *d, va_handle *out)
         if ((size_t)(d->activation - VA_ACT_USER_BASE) >= g_user_act.size()) return fail(VA_EINVAL, "activation module id %d was never registered", d->activation);
         user_act = g_user_act[d->activation - VA_ACT_USER_BASE].launch;
     } else if (d->activation < VA_ACT_SIGMOID || d->activation > VA_ACT_SOFTPLUS) return fail(VA_EUNSUPPORTED, "unknown activation %d", d->activation);
-    const int NL = d->n_layers;
-    std::vector<int> s(d->structure, d->structure + NL), off(NL + 1, 0), woff(NL - 1), boff(NL - 1);
-    long long np = 0;
-    for (int n = 0; n < NL; ++n) {
-        if (s[n] < 1) return fail(VA_EINVAL, "structure[%d]=%d", n, s[n]);
-        off[n + 1] = off[n] + s[n];
-    }
-    for (int n = 0; n < NL - 1; ++n) { woff[n] = (int)np; np += (long long)s[n + 1] * s[n]; boff[n] = (int)np; np += s[n + 1]; }
-    if (np != d->NP) return fail(VA_EINVAL, "NP=%d but the structure holds %lld weights and biases (va_nnet.py:194-207)", d->NP, np);
-    if (d->NPest < 0 || d->NPest > d->NP || !d->P || (d->NPest > 0 && !d->Pidx)) return fail(VA_EINVAL, "bad NPest/P/Pidx");
-    if (d->L_in < 0 || d->L_out < 0 || (d->L_in > 0 && (!d->Lidx_in || !d->data_in)) || (d->L_out > 0 && (!d->Lidx_out || !d->data_out)))
-        return fail(VA_EINVAL, "observed-neuron arrays missing");
-    if (d->L_in + d->L_out < 1) return fail(VA_EINVAL, "no observed neurons: the measurement error divides by Ltot*M (va_nnet.py:173)");
-    const int NDnet = off[NL];
-    const long long nvar = (long long)NDnet * d->M + d->NPest;
-    if (nvar > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_var=%lld does not fit 32-bit indexing", nvar);
-    std::vector<int> lin(s[0], -1), lout(s[NL - 1], -1), pmap(d->NP, -1);
-    for (int l = 0; l < d->L_in; ++l) {
-        if (d->Lidx_in[l] < 0 || d->Lidx_in[l] >= s[0]) return fail(VA_EINVAL, "Lidx_in[%d]=%d outside the input layer", l, d->Lidx_in[l]);
-        lin[d->Lidx_in[l]] = l;
-    }
-    for (int l = 0; l < d->L_out; ++l) {
-        if (d->Lidx_out[l] < 0 || d->Lidx_out[l] >= s[NL - 1]) return fail(VA_EINVAL, "Lidx_out[%d]=%d outside the output layer", l, d->Lidx_out[l]);
-        lout[d->Lidx_out[l]] = l;
-    }
-    for (int k = 0; k < d->NPest; ++k) {
-        if (d->Pidx[k] < 0 || d->Pidx[k] >= d->NP) return fail(VA_EINVAL, "Pidx[%d]=%d outside [0,NP)", k, d->Pidx[k]);
-        if (pmap[d->Pidx[k]] >= 0) return fail(VA_EINVAL, "Pidx[%d]=%d listed twice", k, d->Pidx[k]);
-        pmap[d->Pidx[k]] = k;
-    }
-    const int m = d->lbfgs_m > 0 ? d->lbfgs_m : 10;
-    if (m > MAX_M) return fail(VA_EINVAL, "lbfgs_m=%d > %d", m, MAX_M);
-    const int max_beta = d->max_beta > 0 ? d->max_beta : 1;
-
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (d->device < 0 || d->device >= ndev) return fail(VA_EINVAL, "device %d of %d", d->device, ndev);
-    HIPCHK(hipSetDevice(d->device));
-
-    va_handle h = new va_problem_s();
-    h->device = d->device; h->rhs = -1; h->keep_paths = d->keep_paths; h->is_nnet = true; h->user_act = user_act;
-    if (d->stream) h->stream = (hipStream_t)d->stream;
-    else {
-        hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete h; return fail(VA_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-        h->own_stream = true;
-    }
-    Dev &dv = h->dv;
-    memset(&dv, 0, sizeof dv);
-    NnetDev &nn = h->nn;
-    memset(&nn, 0, sizeof nn);
-    Dims &dm = dv.dm;
-    // to the L-BFGS kernels the unknown vector is one flat run of ND doubles with no tail
-    dm.D = NDnet; dm.N = d->M; dm.ND = (int)nvar; dm.NP = 0; dm.NPest = 0; dm.B = d->batch; dm.m = m;
-    dm.L = d->L_in + d->L_out; dm.N_data = d->M; dm.nskip = 1; dm.disc = VA_DISC_FORWARDMAP;
-    dm.ld = ((dm.ND + 15) / 16) * 16;
-    dm.chunk = VEC_CHUNK; dm.nchunks = (dm.ld + VEC_CHUNK - 1) / VEC_CHUNK;
-    dm.cme = 1.0 / ((double)(d->L_in + d->L_out) * d->M);                 /* va_nnet.py:173 */
-    dm.cfe = d->rf0 / ((double)(NDnet - s[0]) * d->M);                    /* va_nnet.py:255 */
-    dm.rm = d->rm_in; dm.rf0 = d->rf0;
-    dv.ups = UP_OLD + 4 * m; dv.max_beta = max_beta; dv.nbeta = 1;
-    dv.evcols = 8;                 // the network kernels fill EP_ME .. EP_GMAX only
-    dv.o.m = m; dv.o.maxiter = 15000; dv.o.maxls = 20; dv.o.maxfun = 15000; dv.o.ftol = 2.2204460492503131e-09; dv.o.gtol = 1e-5;
-
-    nn.NL = NL; nn.M = d->M; nn.NDnet = NDnet; nn.NDens = NDnet * d->M; nn.NP = d->NP; nn.NPest = d->NPest;
-    nn.act = d->activation; nn.Lin = d->L_in; nn.Lout = d->L_out; nn.rm_in = d->rm_in; nn.rm_out = d->rm_out;
-    // job tables: one entry per 32x32 output tile
-    std::vector<NnetTile> t1, t2, t3;
-    // examples per chunk of the weight-gradient product: 256, doubled while the launch keeps >= 6 workgroups per CU
-    // (each chunk writes a partial of the whole parameter gradient that k_nnet_pred reads back)
-    nn.mch = d->M <= 256 ? ((d->M + NN_KC - 1) / NN_KC) * NN_KC : 256;
-    {
-        long long tiles = 0;
-        int ncu = 256;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d->device) != hipSuccess) ncu = 256;
-        for (int n = 0; n < NL - 1; ++n) tiles += (long long)((s[n + 1] + NN_TILE - 1) / NN_TILE) * ((s[n] + NN_TILE - 1) / NN_TILE);
-        while (nn.mch * 2 <= d->M && tiles * d->batch * ((d->M + 2 * nn.mch - 1) / (2 * nn.mch)) >= 6LL * ncu) nn.mch *= 2;
-    }
-    nn.nmch = (d->M + nn.mch - 1) / nn.mch;
-    auto tile = [&](int n, int r0, int c0, int c) {
-        NnetTile t;
-        memset(&t, 0, sizeof t);
-        t.layer = n; t.r0 = r0; t.c0 = c0; t.chunk = c; t.sn = s[n]; t.offn = off[n];
-        if (n < NL - 1) { t.sn1 = s[n + 1]; t.offn1 = off[n + 1]; t.woff = woff[n]; t.boff = boff[n]; }
-        return t;
-    };
-    // Order of the jobs: workgroup i of a launch runs on XCD i % 8, each with an L2 of its own.  The jobs that read the
-    // same operand rows (the column tiles of one row block; the four tiles of one example chunk) are placed 8 apart --
-    // eight such families at a time, member by member -- so that they meet in ONE L2 and the rows come from HBM once
-    auto place = [&](std::vector<NnetTile> &out, std::vector<std::vector<NnetTile>> &fam) {
-        size_t f0 = 0;
-        while (f0 < fam.size()) {
-            const size_t nf = std::min<size_t>(8, fam.size() - f0);
-            size_t width = 0;
-            for (size_t f = 0; f < nf; ++f) width = std::max(width, fam[f0 + f].size());
-            bool uniform = nf == 8;
-            for (size_t f = 0; f < nf; ++f) uniform = uniform && fam[f0 + f].size() == width;
-            if (uniform)
-                for (size_t k = 0; k < width; ++k)
-                    for (size_t f = 0; f < nf; ++f) out.push_back(fam[f0 + f][k]);
-            else
-                for (size_t f = 0; f < nf; ++f) out.insert(out.end(), fam[f0 + f].begin(), fam[f0 + f].end());
-            f0 += nf;
-        }
-        fam.clear();
-    };
-    std::vector<std::vector<NnetTile>> fam;
-    for (int n = 0; n < NL - 1; ++n) {
-        for (int m0 = 0; m0 < d->M; m0 += NN_TILE) {
-            fam.emplace_back();
-            for (int i0 = 0; i0 < s[n + 1]; i0 += NN_TILE) fam.back().push_back(tile(n, m0, i0, 0));
-        }
-        place(t1, fam);
-    }
-    for (int n = 0; n < NL; ++n) {
-        for (int m0 = 0; m0 < d->M; m0 += NN_TILE) {
-            fam.emplace_back();
-            for (int j0 = 0; j0 < s[n]; j0 += NN_TILE) fam.back().push_back(tile(n, m0, j0, 0));
-        }
-        place(t2, fam);
-    }
-    for (int n = 0; n < NL - 1; ++n) {
-        for (int c = 0; c < nn.nmch; ++c) {
-            fam.emplace_back();
-            for (int i0 = 0; i0 < s[n + 1]; i0 += NN_TILE)
-                for (int j0 = 0; j0 < s[n]; j0 += NN_TILE) fam.back().push_back(tile(n, i0, j0, c));
-        }
-        place(t3, fam);
-    }
-    nn.n1 = (int)t1.size(); nn.n2 = (int)t2.size(); nn.n3 = (int)t3.size();
-    nn.n4 = (d->NP + NN_THREADS - 1) / NN_THREADS;
-    nn.n0 = (nn.NDens + d->NP + NN_THREADS * NN_PACK - 1) / (NN_THREADS * NN_PACK);
-    nn.nraw = nn.n1 + nn.n2 + nn.n4;
-    // small networks: one workgroup per layer does the whole evaluation (k_nnet_small)
-    {
-        int widest = d->M;
-        for (int n = 0; n < NL; ++n) widest = s[n] > widest ? s[n] : widest;
-        nn.small = (widest <= NN_SMALL && NL <= NN_ROWS_DIRECT) ? (widest <= 16 ? 16 : 32) : 0;
-    }
-    if (nn.small) nn.nraw = NL;
-    // layers up to NN_FB_W wide with scalar measurement weights: forward and state-gradient products in one kernel
-    // (k_nnet_fb); its workgroups write the first nfb of the n1 + n2 rows, k_nnet_wfrag zeroes the others
-    std::vector<int> wfoff(2 * (NL - 1), 0);
-    bool fb_ok = false;
-    {
-        int widest = 0, wfsz = 0;
-        for (int n = 0; n < NL; ++n) widest = s[n] > widest ? s[n] : widest;
-        // fragment tables of the two products of every transition: NN_FB_W / 16 column blocks of nn_fb_steps(K) k-steps
-        for (int n = 0; n < NL - 1; ++n) { wfoff[n] = wfsz; wfsz += (NN_FB_W / 16) * nn_fb_steps(s[n]) * 64; }
-        for (int n = 0; n < NL - 1; ++n) { wfoff[NL - 1 + n] = wfsz; wfsz += (NN_FB_W / 16) * nn_fb_steps(s[n + 1]) * 64; }
-        nn.nfb = (d->M + NN_FB_R - 1) / NN_FB_R;
-        nn.wfsz = wfsz;
-        fb_ok = !nn.small && widest <= NN_FB_W && NL <= NN_FB_LAYERS && !d->rm_in_matrix && nn.nfb <= nn.n1 + nn.n2 &&
-                (long long)NDnet * d->M < (1LL << 31);
-        {
-            int ncu = 256;
-            if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d->device) != hipSuccess) ncu = 256;
-            nn.fb_slots = ncu * NN_FB_WGS; nn.fb_stagger = 0;
-        }
-        // on when its blocks of NN_FB_R examples fill the chip at least once (a workgroup walks ALL layers of its block:
-        // with few blocks the separate kernels, one workgroup per layer and tile, have more in flight); va_problem_tune
-        // switches it either way (c5x, 1024 workgroups: 637 against 709 us per evaluation, profiles/r04_nnet_fused.txt)
-        // (not for softplus -- log1p / exp / expm1 spill 28 registers there: 830 against 809 us -- nor, unasked, for a generated
-        // activation, whose register needs nobody has looked at)
-        nn.fused = fb_ok && (long long)nn.nfb * d->batch >= nn.fb_slots && d->activation != NNET_SOFTPLUS && d->activation < NNET_USER;
-    }
-    const bool fold_rows = nn.nraw > NN_ROWS_DIRECT;      // k_ls sums the rows with one wave: keep them few
-    dm.nprow = fold_rows ? NN_RED_ROWS : nn.nraw;
-    dm.ntiles = dm.nprow; dm.T = NN_TILE; dm.emode = 0;
-
-    int rc = VA_OK;
-    const size_t B = dm.B;
-    int *s_d = nullptr, *off_d = nullptr, *woff_d = nullptr, *boff_d = nullptr, *lin_d = nullptr, *lout_d = nullptr, *pmap_d = nullptr;
-    double *din_d = nullptr, *dout_d = nullptr, *P_d = nullptr;
-    NnetTile *t1_d = nullptr, *t2_d = nullptr, *t3_d = nullptr;
-#define TRY(x) do { rc = (x); if (rc) { va_problem_destroy(h); return rc; } } while (0)
-#define H2D(dst, src, n, T) do { hipError_t e_ = hipMemcpyAsync(dst, src, sizeof(T) * (n), hipMemcpyHostToDevice, h->stream); \
-        if (e_ != hipSuccess) { va_problem_destroy(h); return fail(VA_EHIP, "H2D %s: %s", #dst, hipGetErrorString(e_)); } } while (0)
-    TRY(h->alloc(&s_d, NL)); TRY(h->alloc(&off_d, NL + 1)); TRY(h->alloc(&woff_d, NL - 1)); TRY(h->alloc(&boff_d, NL - 1));
-    TRY(h->alloc(&lin_d, s[0])); TRY(h->alloc(&lout_d, s[NL - 1])); TRY(h->alloc(&pmap_d, d->NP));
-    TRY(h->alloc(&din_d, (size_t)d->M * d->L_in)); TRY(h->alloc(&dout_d, (size_t)d->M * d->L_out));
-    TRY(h->alloc(&P_d, B * d->NP)); TRY(h->alloc(&nn.Pw, B * d->NP));
-    TRY(h->alloc(&nn.delta, B * dm.ld));
-    TRY(h->alloc(&nn.Xw, B * dm.ld));
-    if (fold_rows) TRY(h->alloc(&nn.raw, B * nn.nraw * EP_GP));
-    TRY(h->alloc(&nn.gpart, B * nn.nmch * (size_t)d->NP));
-    int *wfoff_d = nullptr;
-    if (fb_ok) {
-        TRY(h->alloc(&nn.Wf, B * (size_t)nn.wfsz));
-        TRY(h->alloc(&wfoff_d, 2 * (NL - 1)));
-        TRY(h->alloc(&dv.pz.stamps, (size_t)PZ_NSTAMP));       // (measurement builds of k_nnet_fb: va_measure.h)
-        TRY(h->alloc(&nn.fb_cu, (size_t)16));
-    }
-    TRY(h->alloc(&t1_d, t1.size())); TRY(h->alloc(&t2_d, t2.size())); TRY(h->alloc(&t3_d, t3.size()));
-    TRY(alloc_solver_state(h, max_beta, d->keep_paths));
-    H2D(s_d, s.data(), NL, int); H2D(off_d, off.data(), NL + 1, int);
-    H2D(woff_d, woff.data(), NL - 1, int); H2D(boff_d, boff.data(), NL - 1, int);
-    H2D(lin_d, lin.data(), s[0], int); H2D(lout_d, lout.data(), s[NL - 1], int); H2D(pmap_d, pmap.data(), d->NP, int);
-    if (d->L_in) H2D(din_d, d->data_in, (size_t)d->M * d->L_in, double);
-    if (d->L_out) H2D(dout_d, d->data_out, (size_t)d->M * d->L_out, double);
-    H2D(P_d, d->P, B * d->NP, double);
-    if (fb_ok) { H2D(wfoff_d, wfoff.data(), 2 * (NL - 1), int); nn.wfoff = wfoff_d; }
-    H2D(t1_d, t1.data(), t1.size(), NnetTile); H2D(t2_d, t2.data(), t2.size(), NnetTile);
-    if (!t3.empty()) H2D(t3_d, t3.data(), t3.size(), NnetTile);
-    nn.s = s_d; nn.off = off_d; nn.woff = woff_d; nn.boff = boff_d; nn.lmap_in = lin_d; nn.lmap_out = lout_d;
-    nn.pmap = pmap_d; nn.din = din_d; nn.dout = dout_d; nn.Pfix = P_d; nn.t1 = t1_d; nn.t2 = t2_d; nn.t3 = t3_d;
-    if (d->rm_in_matrix) {
-        // full measurement matrices (va_nnet.py:136-139): the kernels walk the layer's observed neurons
-        double *ri = nullptr, *ro = nullptr; int *li = nullptr, *lo = nullptr;
-        TRY(h->alloc(&ri, (size_t)d->L_in * d->L_in + 1)); TRY(h->alloc(&ro, (size_t)d->L_out * d->L_out + 1));
-        TRY(h->alloc(&li, d->L_in + 1)); TRY(h->alloc(&lo, d->L_out + 1));
-        if (d->L_in) { H2D(ri, d->rm_in_matrix, (size_t)d->L_in * d->L_in, double); H2D(li, d->Lidx_in, d->L_in, int); }
-        if (d->L_out) { H2D(ro, d->rm_out_matrix, (size_t)d->L_out * d->L_out, double); H2D(lo, d->Lidx_out, d->L_out, int); }
-        nn.rmm_in = ri; nn.rmm_out = ro; nn.lidx_in = li; nn.lidx_out = lo;
-    }
-    if (fb_ok) {
-        const hipError_t e = prepare_nnet_fb(nn, user_act);
-        if (e != hipSuccess) { (void)hipGetLastError(); nn.Wf = nullptr; }      // (the tune knob then refuses)
-    }
-    TRY(finish_create(h));
-#undef TRY
-#undef H2D
-    *out = h;
+    NnetPlan plan;       // (its tables are uploaded: alive until finish_create has synchronised the stream, or, on a failing
+                         // return, until the owner declared after it has destroyed the handle)
+    const char *why = "";
+    if (int rc = plan_nnet(d, cu_count(d->device), plan, &why)) return fail(rc, "%s", why);
+    HandleOwner h;
+    TRY(begin_create(d->device, d->stream, d->lbfgs_m, d->max_beta, d->keep_paths, h));
+    h->rhs = -1; h->is_nnet = true; h->user_act = user_act;
+    fill_nnet_dims(h.get(), d, plan);
+    TRY(create_nnet_image(h.get(), d, plan));
+    TRY(finish_create(h.get()));
+    *out = h.release();
     return VA_OK;
 }
 

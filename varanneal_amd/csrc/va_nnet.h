@@ -5,40 +5,9 @@
 // the ODE path (Dims.ND = M*NDnet + NPest, Dims.NPest = 0); only the evaluator differs.
 #pragma once
 #include "va_device.h"
+#include "va_nnet_geo.h"      // NN_* constants, NnetTile, and the host's launch plan
 
 namespace va {
-
-enum { NNET_SIGMOID = 0, NNET_TANH = 1, NNET_LINEAR = 2, NNET_RELU = 3, NNET_SOFTPLUS = 4,
-       NNET_USER = 1000 };   // >= NNET_USER: a generated activation module (va_act_load_module)
-
-constexpr int NN_TILE = 64;      // workgroup output tile: 2 x 2 waves, each 2 x 2 MFMA blocks of 16x16
-constexpr int NN_KC = 32;        // K elements staged in LDS per step
-constexpr int NN_THREADS = 256;
-constexpr int NN_PACK = 8;       // elements per thread of the trial-point kernel (k_nnet_pack)
-
-// layers up to NN_FB_W wide: the forward product and the state-gradient product of every transition in ONE kernel
-// (k_nnet_fb, va_nnet_kernels.h): a workgroup marches a block of NN_FB_R examples through the layers
-#ifndef NN_FB_ROWS
-#define NN_FB_ROWS 32
-#endif
-#ifndef NN_FB_THR
-#define NN_FB_THR 256
-#endif
-// NN_FB_THREADS / 64 waves share the NN_FB_W / 16 column blocks of a layer; NN_FB_WGS workgroups per CU (their LDS: two
-// operand images of NN_FB_R rows)
-constexpr int NN_FB_R = NN_FB_ROWS, NN_FB_W = 128, NN_FB_THREADS = NN_FB_THR, NN_FB_PITCH = NN_FB_W + 2;
-constexpr int NN_FB_WGS = NN_FB_R == 32 ? 2 : 1;
-constexpr int NN_FB_LAYERS = 64; // most layers its per-layer table in LDS holds
-constexpr int NN_FB_PF = 8;      // k-steps the B fragments of its products are requested ahead
-// k-steps a fragment table holds per column block for a product over K: whole groups of NN_FB_PF, one group of zeros behind
-constexpr int nn_fb_steps(int K) { return (((K + 3) / 4 + NN_FB_PF - 1) / NN_FB_PF) * NN_FB_PF + NN_FB_PF; }
-
-constexpr int NN_SMALL = 32;         // widest layer / most examples the single-kernel path handles
-constexpr int NN_ROWS_DIRECT = 64;   // partial rows per seed the line-search kernel reduces itself
-constexpr int NN_RED_ROWS = 32;      // rows left by k_nnet_rows when there are more
-// one workgroup's job: rows [r0, r0+64) x columns [c0, c0+64) of a layer's product
-// (layer metadata rides in the entry so a workgroup needs ONE dependent load before its data)
-struct NnetTile { int layer, r0, c0, chunk, sn, sn1, offn, offn1, woff, boff, pad0, pad1; };
 
 struct NnetDev {
     int NL, M, NDnet, NDens, NP, NPest, act;
