@@ -222,7 +222,7 @@ def lib():
     L.va_debug_read_persist.restype = C.c_int
     L.va_problem_persistent.argtypes = [h, c_ip, c_ip]
     L.va_problem_persistent.restype = C.c_int
-    for fn in ("va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_tune", "va_problem_tune", "va_problem_create", "va_nnet_problem_create",
+    for fn in ("va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_tune", "va_problem_create", "va_nnet_problem_create",
                "va_problem_info", "va_action_grad",
                "va_minimize_lbfgs", "va_anneal", "va_get_minpath", "va_eval_timed", "va_eval_timed_prepare",
                "va_get_counters", "va_debug_read_partials", "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed",

@@ -74,9 +74,10 @@ class HIPmin(object):
     def min_lm_scipy(self, XP0, xtrace=None):
         raise NotImplementedError("min_lm_scipy is unfinished upstream (_autodiffmin.py:145-160)")
 
-    def _host_minimise(self, meth, XP0):
+    def _scipy_minimize(self, meth, x0, rf):
+        """THE SciPy call of this package (_autodiffmin.py:85-86, :109-110, :133-134): one seed, on the host, the
+        device evaluator at RF0 * rf in the role of A_gradA_taped.  Returns SciPy's result object."""
         import scipy.optimize as opt
-        rf = self._rf_now()
 
         def fg(z):
             A, me, fe, g = self._pb.action_grad(z[None, :], rf)
@@ -84,5 +85,8 @@ class HIPmin(object):
         kw = dict(method=meth, jac=True, options=self.opt_args)
         if meth != 'CG':
             kw["bounds"] = self.bounds
-        res = opt.minimize(fg, XP0, **kw)
+        return opt.minimize(fg, x0, **kw)
+
+    def _host_minimise(self, meth, XP0):
+        res = self._scipy_minimize(meth, XP0, self._rf_now())
         return res.x, float(res.fun), int(res.status)

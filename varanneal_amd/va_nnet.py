@@ -28,12 +28,10 @@ with structure[n+1] (va_nnet.py:534 uses structure[n], equal only for uniform ne
 `exitflags` are written.  Kept: `init_to_data` overwrites the caller's X0 (va_nnet.py:423-430);
 `anneal()` always re-initialises (va_nnet.py:276, :450 typo).
 """
-import time
-
 import numpy as np
 
 from . import _capi
-from ._hipmin import HIPmin, alpha_pow as _alpha_pow
+from ._ladder import LadderAnnealer
 
 ACT_IMPL = {
     "sigmoid": lambda x, W, b: 1.0 / (1.0 + np.exp(-(np.dot(W, x) + b))),
@@ -69,15 +67,13 @@ def recognise_activation(f):
     return None
 
 
-class Annealer(HIPmin):
+class Annealer(LadderAnnealer):
     def __init__(self):
-        self.taped = False
-        self.annealing_initialized = False
+        LadderAnnealer.__init__(self)
         self.M = 0
         self.structure = None
         self.f = None
         self._act = None
-        self._pb = None
 
     # ------------------------------------------------------------------ setup (va_nnet.py:59-106)
     def set_structure(self, structure):
@@ -117,20 +113,7 @@ class Annealer(HIPmin):
         if self.annealing_initialized is False:
             self.anneal_init(X0, P0, alpha, beta_array, RM, RF0, Pidx, Lidx, init_to_data, action, disc,
                              method, bounds, opt_args, adolcID, device=device, verbose=verbose)
-        if fused is None:
-            fused = self._device_minimiser
-        if fused:
-            if not self._device_minimiser:
-                raise ValueError("fused=True needs method='L-BFGS-B' with bounds=None")
-            self._anneal_fused()
-            return
-        for _ in self.beta_array:
-            if self.verbose:
-                print('------------------------------')
-                print('Step %d of %d' % (self.betaidx + 1, len(self.beta_array)))
-                print('beta = %d, RF = %.8e' % (self.beta, self.RF))
-                print('')
-            self.anneal_step()
+        self._run_ladder(fused)
 
     def anneal_init(self, X0, P0, alpha, beta_array, RM, RF0, Pidx, Lidx=None,
                     init_to_data=True, action='A_gaussian', disc='forwardmap',
@@ -194,159 +177,28 @@ class Annealer(HIPmin):
                              % (self.M, self.L[0], self.M, self.L[1]))
         self.RM = RM
 
-        self.alpha = alpha
-        self.beta_array = np.asarray(beta_array)
-        self.betaidx = 0
-        self.beta = self.beta_array[0]
-        self.Nbeta = len(self.beta_array)
         if RF0 is not None:
             self.RF0 = RF0
-        self.RF = self.RF0 * _alpha_pow(self.alpha, self.beta)
-        self._rf_scale = _alpha_pow(self.alpha, self.beta_array)
+        self._ladder_init(alpha, np.asarray(beta_array))
 
         if init_to_data:                                               # va_nnet.py:423-430
             Xv = Xf.reshape(self.B, self.M, self.NDnet)
             Xv[:, :, self.Lidx[0]] = self.data_in
             Xv[:, :, self.NDnet - s[-1] + self.Lidx[1]] = self.data_out
 
-        self._mp = np.zeros((self.B, self.Nbeta, self.NDens + self.NP))
-        self._mp[:, 0, :self.NDens] = Xf
-        self._mp[:, 0, self.NDens:] = Pf
-        self._A = np.zeros((self.B, self.Nbeta)); self._me = np.zeros((self.B, self.Nbeta))
-        self._fe = np.zeros((self.B, self.Nbeta))
-        self._flags = np.zeros((self.B, self.Nbeta), dtype=np.int8)
-        self._nit = np.zeros((self.B, self.Nbeta), dtype=np.int32)
-        self._nfev = np.zeros((self.B, self.Nbeta), dtype=np.int64)
-        self._Pfull = np.array(Pf, dtype=np.float64)
+        self._estpos = list(self.Pidx)                                 # inside the NP weights and biases
+        self._alloc_tables(Xf, Pf)
         self.adolcID = adolcID                                         # accepted, unused: there is no tape
         self._device_minimiser = (method == 'L-BFGS-B' and bounds is None)
         if not self._device_minimiser and self.B != 1:
             raise ValueError("bounds / NCG / TNC run SciPy on the host around the device evaluator: one seed only")
 
-        if self._pb is not None:
-            self._pb.close()
+        self.close()
         self._pb = _capi.NnetProblem(self.B, s, self.data_in, self.data_out, self.Lidx, RM, float(self.RF0),
                                      self._Pfull, self.Pidx, act=self._act,
                                      lbfgs_m=int((opt_args or {}).get("maxcor", 10)), max_beta=self.Nbeta,
                                      keep_paths=1, device=device)
         self.initalized = True                                         # sic (va_nnet.py:450)
-
-    def _view(self, a):
-        return a if self._batched else a[0]
-
-    minpaths = property(lambda self: self._view(self._mp))
-    A_array = property(lambda self: self._view(self._A))
-    me_array = property(lambda self: self._view(self._me))
-    fe_array = property(lambda self: self._view(self._fe))
-    exitflags = property(lambda self: self._view(self._flags))
-    nit_array = property(lambda self: self._view(self._nit))
-    nfev_array = property(lambda self: self._view(self._nfev))
-
-    def _xp0(self, k):
-        """va_nnet.py:460-473"""
-        src = self._mp[:, k - 1 if k > 0 else 0]
-        return np.concatenate([src[:, :self.NDens], src[:, self.NDens:][:, self.Pidx]], axis=1)
-
-    def _store(self, k, x, A, me, fe, flag, nit, nfev):
-        self._Pfull[:, self.Pidx] = x[:, self.NDens:]                  # va_nnet.py:493-499
-        if self._batched:
-            self.P[:, self.Pidx] = x[:, self.NDens:]
-        else:
-            self.P[self.Pidx] = x[0, self.NDens:]
-        self._A[:, k] = A; self._me[:, k] = me; self._fe[:, k] = fe      # :502-504
-        self._mp[:, k, :self.NDens] = x[:, :self.NDens]; self._mp[:, k, self.NDens:] = self._Pfull   # :505
-        self._flags[:, k] = flag; self._nit[:, k] = nit; self._nfev[:, k] = nfev
-
-    def anneal_step(self):
-        """One ladder step for every seed (va_nnet.py:452-523)."""
-        k = self.betaidx
-        XP0 = self._xp0(k)
-        rf = float(self._rf_scale[k])
-        t0 = time.time()
-        if self._device_minimiser:
-            r = self._pb.minimize_lbfgs(XP0, rf, self.opt_args)
-            x, A, me, fe, flag, nit, nfev = r["x"], r["A"], r["me"], r["fe"], r["status"], r["nit"], r["nfev"]
-        else:
-            x, A, me, fe, flag, nit, nfev = self._minimize_scipy(XP0, rf)
-        self._store(k, x, A, me, fe, flag, nit, nfev)
-        if self.verbose:
-            print("Optimization complete!")
-            print("Time = {0} s".format(time.time() - t0))
-            print("Exit flag = {0}".format(flag[0] if self.B == 1 else flag))
-            print("Iterations = {0}".format(nit[0] if self.B == 1 else nit))
-            print("Obj. function value = {0}\n".format(A[0] if self.B == 1 else A))
-        if self.betaidx < len(self.beta_array) - 1:                    # va_nnet.py:508-511
-            self.betaidx += 1
-            self.beta = self.beta_array[self.betaidx]
-            self.RF = self.RF0 * _alpha_pow(self.alpha, self.beta)
-        self.taped = False
-
-    def _anneal_fused(self):
-        """Remaining ladder steps in one va_anneal call; seeds advance independently."""
-        k0 = self.betaidx
-        t0 = time.time()
-        r = self._pb.anneal(self._xp0(k0), self._rf_scale[k0:], self.opt_args, want_paths=True)
-        nb = self.Nbeta - k0
-        self._A[:, k0:] = r["A"]; self._me[:, k0:] = r["me"]; self._fe[:, k0:] = r["fe"]
-        self._flags[:, k0:] = r["status"]; self._nit[:, k0:] = r["nit"]; self._nfev[:, k0:] = r["nfev"]
-        mp = r["minpaths"]                                             # [B][nb][NDens + NPest]
-        self._mp[:, k0:, :self.NDens] = mp[:, :, :self.NDens]
-        self._mp[:, k0:, self.NDens:] = self._Pfull[:, None, :]
-        self._mp[:, k0:, [self.NDens + j for j in self.Pidx]] = mp[:, :, self.NDens:]
-        self._Pfull[:] = self._mp[:, -1, self.NDens:]
-        if self._batched:
-            self.P[:, self.Pidx] = self._Pfull[:, self.Pidx]
-        else:
-            self.P[self.Pidx] = self._Pfull[0, self.Pidx]
-        self.betaidx = self.Nbeta - 1
-        self.beta = self.beta_array[self.betaidx]
-        self.RF = self.RF0 * _alpha_pow(self.alpha, self.beta)
-        if self.verbose:
-            print("Ladder of %d steps x %d seed(s): %.3f s, %d action+gradient evaluations"
-                  % (nb, self.B, time.time() - t0, int(self._nfev[:, k0:].sum())))
-
-    def _minimize_scipy(self, XP0, rf):
-        """bounds / NCG / TNC: SciPy exactly as _autodiffmin.py:72-146 calls it, the device
-        kernels in the role of A_gradA_taped."""
-        import scipy.optimize as opt
-        meth = {'L-BFGS-B': 'L-BFGS-B', 'NCG': 'CG', 'TNC': 'TNC'}[self.method]
-
-        def fg(z):
-            A, me, fe, g = self._pb.action_grad(z[None, :], rf)
-            return A[0], g[0]
-        kw = dict(method=meth, jac=True, options=self.opt_args)
-        if meth != 'CG':
-            kw["bounds"] = self.bounds
-        res = opt.minimize(fg, XP0[0], **kw)
-        A, me, fe, _ = self._pb.action_grad(res.x[None, :], rf, want_grad=False)
-        return (res.x[None, :], np.array([res.fun]), me, fe, np.array([res.status]), np.array([res.nit]),
-                np.array([res.nfev]))
-
-    # ------------------------------------------------------------------ S1 evaluator
-    def _eval(self, XP, want_grad):
-        XP = np.asarray(XP, dtype=np.float64)
-        single = XP.ndim == 1
-        X2 = np.tile(XP, (self.B, 1)) if single else XP
-        A, me, fe, g = self._pb.action_grad(X2, float(self._rf_scale[self.betaidx]), want_grad=want_grad)
-        if single:
-            return A[0], me[0], fe[0], (g[0] if want_grad else None)
-        return A, me, fe, g
-
-    def A_gaussian(self, XP):
-        return self._eval(XP, False)[0]
-
-    A = A_gaussian
-
-    def me_gaussian(self, XP):
-        return self._eval(XP, False)[1]
-
-    def fe_gaussian(self, XP):
-        return self._eval(XP, False)[2]
-
-    def close(self):
-        if self._pb is not None:
-            self._pb.close()
-            self._pb = None
 
     # ------------------------------------------------------------------ savers (va_nnet.py:528-650)
     def _layers(self, row):
@@ -367,6 +219,14 @@ class Annealer(HIPmin):
                         out[a, b, c] = np.asarray(xc, dtype=dtype)
             return out
 
+    @staticmethod
+    def _save_packed(filename, arr, fmt):
+        """the tail of save_states / save_io: `arr` is packed already (possibly an object array)"""
+        if filename.endswith('.npy'):
+            np.save(filename, arr, allow_pickle=True)
+        else:
+            np.savetxt(filename, arr.reshape(-1, arr.shape[-1]), fmt=fmt)
+
     def _one(self):
         if self._batched:
             raise ValueError("savers write one seed's results; index the arrays (minpaths[b], ...) for a batch")
@@ -377,11 +237,7 @@ class Annealer(HIPmin):
         mp = self._one()
         nested = [[self._layers(mp[b, m * self.NDnet:(m + 1) * self.NDnet]) for b in range(self.Nbeta)]
                   for m in range(self.M)]
-        arr = self._pack(nested, dtype)
-        if filename.endswith('.npy'):
-            np.save(filename, arr, allow_pickle=True)
-        else:
-            np.savetxt(filename, arr.reshape(-1, arr.shape[-1]), fmt=fmt)
+        self._save_packed(filename, self._pack(nested, dtype), fmt)
 
     def save_io(self, filename, dtype=np.float64, fmt="%.8e"):
         """(M, Nbeta, 2): input- and output-layer states (va_nnet.py:553-577)."""
@@ -390,20 +246,12 @@ class Annealer(HIPmin):
         nested = [[[mp[b, m * self.NDnet:m * self.NDnet + s[0]],
                     mp[b, (m + 1) * self.NDnet - s[-1]:(m + 1) * self.NDnet]] for b in range(self.Nbeta)]
                   for m in range(self.M)]
-        arr = self._pack(nested, dtype)
-        if filename.endswith('.npy'):
-            np.save(filename, arr, allow_pickle=True)
-        else:
-            np.savetxt(filename, arr.reshape(-1, arr.shape[-1]), fmt=fmt)
+        self._save_packed(filename, self._pack(nested, dtype), fmt)
 
     def save_params(self, filename, dtype=np.float64, fmt="%.8e"):
         if self.NPest == 0:
             print("WARNING: You did not estimate any parameters.  Writing fixed parameter values to file anyway.")
-        savearray = np.array(self._one()[:, self.NDens:])
-        if filename.endswith('.npy'):
-            np.save(filename, savearray.astype(dtype))
-        else:
-            np.savetxt(filename, savearray, fmt=fmt)
+        self._save_array(filename, self._one()[:, self.NDens:], dtype, fmt, self.NP)
 
     def weights_biases(self, beta_idx=-1, seed=0):
         """([W_0, ...], [b_0, ...]) of one ladder step (layout va_nnet.py:194-207)."""
@@ -437,17 +285,4 @@ class Annealer(HIPmin):
     def save_action_errors(self, filename, cmpt=0, dtype=np.float64, fmt="%.8e"):
         """(Nbeta, 5) = [beta, A, me, fe, fe/RF] (va_nnet.py:628-650)."""
         self._one()
-        savearray = np.zeros((self.Nbeta, 5))
-        savearray[:, 0] = self.beta_array
-        savearray[:, 1] = self._A[0]
-        savearray[:, 2] = self._me[0]
-        savearray[:, 3] = self._fe[0]
-        savearray[:, 4] = self._fe[0] / (self.RF0 * _alpha_pow(self.alpha, self.beta_array))
-        if filename.endswith('.npy'):
-            np.save(filename, savearray.astype(dtype))
-        else:
-            np.savetxt(filename, savearray, fmt=fmt)
-
-    def gen_xtrace(self):
-        """kept for API compatibility (va_nnet.py:655-660); nothing is taped here"""
-        return np.random.rand(self.NDens + self.NPest)
+        LadderAnnealer.save_action_errors(self, filename, cmpt, dtype, fmt)

@@ -40,23 +40,19 @@ row, which is what upstream's Simpson-Hermite branch does and its other branches
 """
 from __future__ import print_function
 
-import time
-
-import os
-
 import numpy as np
 
 from . import _capi, rhs as _rhs
-from ._hipmin import HIPmin, alpha_pow as _alpha_pow
+from ._ladder import LadderAnnealer
 
 _DISCS = ("euler", "trapezoid", "SimpsonHermite", "forwardmap")
 
 
-class Annealer(HIPmin):
+class Annealer(LadderAnnealer):
+    _print_exit_message = True
+
     def __init__(self):
-        self.taped = False                    # reference attribute (va_ode.py:53); unused here
-        self.annealing_initialized = False
-        self._pb = None
+        LadderAnnealer.__init__(self)
         self.stim = None
 
     # ------------------------------------------------------------------ model / data
@@ -149,21 +145,8 @@ class Annealer(HIPmin):
             self.anneal_init(X0, P0, alpha, beta_array, RM, RF0, Lidx, Pidx, dt_model,
                              init_to_data, action, disc, method, bounds, opt_args, adolcID,
                              device=device, verbose=verbose, bounded_minimiser=bounded_minimiser)
-        tracking = any(t is not None for t in (track_paths, track_params, track_action_errors))
-        if fused is None:
-            fused = (not tracking) and self._device_minimiser
-        if fused:
-            if not self._device_minimiser:
-                raise ValueError("fused=True needs method='L-BFGS-B' with bounds=None")
-            self._anneal_fused()
-            return
-        for _ in self.beta_array:
-            if self.verbose:
-                print('------------------------------')
-                print('Step %d of %d' % (self.betaidx + 1, len(self.beta_array)))
-                print('beta = %d, RF = %.8e' % (self.beta, self._rf_print()))
-                print('')
-            self.anneal_step()
+
+        def track():
             if track_paths is not None:
                 self.save_paths(track_paths['filename'], track_paths.get('dtype', np.float64),
                                 track_paths.get('fmt', "%.8e"))
@@ -175,6 +158,8 @@ class Annealer(HIPmin):
                                         track_action_errors.get('cmpt', 0),
                                         track_action_errors.get('dtype', np.float64),
                                         track_action_errors.get('fmt', "%.8e"))
+        tracking = any(t is not None for t in (track_paths, track_params, track_action_errors))
+        self._run_ladder(fused, track if tracking else None)
 
     def anneal_init(self, X0, P0, alpha, beta_array, RM, RF0, Lidx, Pidx, dt_model=None,
                     init_to_data=True, action='A_gaussian', disc='trapezoid',
@@ -298,13 +283,7 @@ class Annealer(HIPmin):
             self.RF0 = float(RF0)
 
         # ladder (va_ode.py:643-650; beta is truncated to uint16 upstream, kept)
-        self.alpha = alpha
-        self.beta_array = np.array(beta_array, dtype=np.uint16)
-        self.Nbeta = len(self.beta_array)
-        self._rf_scale = _alpha_pow(self.alpha, self.beta_array)
-        self.betaidx = 0
-        self.beta = self.beta_array[0]
-        self.RF = self.RF0 * _alpha_pow(self.alpha, self.beta)
+        self._ladder_init(alpha, np.array(beta_array, dtype=np.uint16))
 
         # bounds (va_ode.py:582-605): expanded exactly as upstream, used by the SciPy route
         if bounds is not None:
@@ -330,22 +309,13 @@ class Annealer(HIPmin):
         # initial path (va_ode.py:666-693); init_to_data overwrites the caller's X0 in place, as upstream
         if init_to_data is True:
             X0[..., ::self.merr_nskip, self.Lidx] = self.Y[:]
-        ND = self.N_model * self.D
-        Xf = np.reshape(np.asarray(X0, dtype=np.float64), (self.B, ND))
+        Xf = np.reshape(np.asarray(X0, dtype=np.float64), (self.B, self.N_model * self.D))
         npw = self.N_model * self.NP if self._tdp else self.NP          # stored parameter block, time-major
         Pf = np.reshape(P0, (self.B, npw))
         # positions of the estimated entries inside that block, in path-vector order (va_ode.py:183-188)
         self._estpos = ([n * self.NP + k for n in range(self.N_model) for k in self.Pidx] if self._tdp
                         else list(self.Pidx))
-        self._mp = np.zeros((self.B, self.Nbeta, ND + npw), dtype=np.float64)
-        self._mp[:, 0, :ND] = Xf
-        self._mp[:, 0, ND:] = Pf
-        self._A = np.zeros((self.B, self.Nbeta)); self._me = np.zeros((self.B, self.Nbeta))
-        self._fe = np.zeros((self.B, self.Nbeta))
-        self._flags = np.zeros((self.B, self.Nbeta), dtype=np.int8)
-        self._nit = np.zeros((self.B, self.Nbeta), dtype=np.int32)
-        self._nfev = np.zeros((self.B, self.Nbeta), dtype=np.int64)
-        self._Pfull = np.array(Pf, dtype=np.float64)
+        self._alloc_tables(Xf, Pf)
         self.adolcID = adolcID                        # accepted, unused: there is no tape
 
         if rhs_id is None:
@@ -369,8 +339,7 @@ class Annealer(HIPmin):
             self._rhs_module = mod
 
         # device image
-        if self._pb is not None:
-            self._pb.close()
+        self.close()
         self._pb = _capi.Problem(self.B, self.D, self.N_model, np.asarray(self.Y, dtype=np.float64),
                                  self.Lidx, float(self.dt_model), self.RM, self.RF0,
                                  self._Pfull.reshape(self.B, self.N_model, self.NP) if self._tdp else self._Pfull,
@@ -382,169 +351,36 @@ class Annealer(HIPmin):
                                  bounds=self.bounds if self._device_bounds else None)
         self.initalized = True                        # sic (va_ode.py:705)
 
-    # views with the reference's shapes
-    def _view(self, a):
-        return a if self._batched else a[0]
-
-    minpaths = property(lambda self: self._view(self._mp))
-    A_array = property(lambda self: self._view(self._A))
-    me_array = property(lambda self: self._view(self._me))
-    fe_array = property(lambda self: self._view(self._fe))
-    exitflags = property(lambda self: self._view(self._flags))
-    nit_array = property(lambda self: self._view(self._nit))
-    nfev_array = property(lambda self: self._view(self._nfev))
-
-    def _rf_print(self):
-        return float(np.ravel(self.RF)[0])
-
-    def _xp0(self, k):
-        """start point of ladder step k: previous minimiser, estimated parameters only
-        (va_ode.py:715-732)"""
-        ND = self.N_model * self.D
-        src = self._mp[:, k - 1 if k > 0 else 0]
-        return np.concatenate([src[:, :ND], src[:, ND:][:, self._estpos]], axis=1)
-
-    def _write_back_P(self):
-        """estimated values into the caller's P array (va_ode.py:750-769)"""
-        if self.NPest == 0:
-            return
-        if self._tdp:
-            est = self._Pfull.reshape(self.B, self.N_model, self.NP)[:, :, self.Pidx]
-            if self._batched:
-                self.P[:, :, self.Pidx] = est
-            else:
-                self.P[:, self.Pidx] = est[0]
-        elif self._batched:
-            self.P[:, self.Pidx] = self._Pfull[:, self.Pidx]
-        else:
-            self.P[self.Pidx] = self._Pfull[0, self.Pidx]
-
-    def _store(self, k, x, A, me, fe, flag, nit, nfev):
-        ND = self.N_model * self.D
-        self._Pfull[:, self._estpos] = x[:, ND:]
-        self._write_back_P()
-        self._A[:, k] = A; self._me[:, k] = me; self._fe[:, k] = fe      # :773-775
-        self._mp[:, k, :ND] = x[:, :ND]; self._mp[:, k, ND:] = self._Pfull  # :776
-        self._flags[:, k] = flag; self._nit[:, k] = nit; self._nfev[:, k] = nfev
-
-    def anneal_step(self):
-        """One ladder step for every seed (va_ode.py:707-789)."""
-        k = self.betaidx
-        XP0 = self._xp0(k)
-        rf = float(self._rf_scale[k])
-        t0 = time.time()
-        if self._device_minimiser:
-            r = self._pb.minimize_lbfgs(XP0, rf, self.opt_args)
-            x, A, me, fe, flag, nit, nfev = r["x"], r["A"], r["me"], r["fe"], r["status"], r["nit"], r["nfev"]
-            msg = None
-        else:
-            x, A, me, fe, flag, nit, nfev, msg = self._minimize_scipy(XP0, rf)
-        self._store(k, x, A, me, fe, flag, nit, nfev)
-        if self.verbose:
-            print("Optimization complete!")
-            print("Time = {0} s".format(time.time() - t0))
-            print("Exit flag = {0}".format(flag[0] if self.B == 1 else flag))
-            if msg is not None:
-                print("Exit message: {0}".format(msg))
-            print("Iterations = {0}".format(nit[0] if self.B == 1 else nit))
-            print("Obj. function value = {0}\n".format(A[0] if self.B == 1 else A))
-        if self.betaidx < len(self.beta_array) - 1:                   # va_ode.py:779-782
-            self.betaidx += 1
-            self.beta = self.beta_array[self.betaidx]
-            self.RF = self.RF0 * _alpha_pow(self.alpha, self.beta)
-        self.taped = False
-
-    def _anneal_fused(self):
-        """Remaining ladder steps in one va_anneal call; seeds advance independently."""
-        k0 = self.betaidx
-        XP0 = self._xp0(k0)
-        t0 = time.time()
-        # the minimising path of every step (va_ode.py:776) comes back in the same call
-        r = self._pb.anneal(XP0, self._rf_scale[k0:], self.opt_args, want_paths=True)
-        ND = self.N_model * self.D
-        nb = self.Nbeta - k0
-        self._A[:, k0:] = r["A"]; self._me[:, k0:] = r["me"]; self._fe[:, k0:] = r["fe"]
-        self._flags[:, k0:] = r["status"]; self._nit[:, k0:] = r["nit"]; self._nfev[:, k0:] = r["nfev"]
+    def _fused_paths(self, k0, mp):
         if self._tdp:                                 # rows come back as [X | p_est], time-major
-            mp = r["minpaths"]
-            self._mp[:, k0:, :ND] = mp[:, :, :ND]
-            self._mp[:, k0:, ND:] = self._Pfull[:, None, :]
-            self._mp[:, k0:, [ND + j for j in self._estpos]] = mp[:, :, ND:]
-        else:
-            self._mp[:, k0:] = r["minpaths"]
-        self._Pfull[:] = self._mp[:, -1, ND:]
-        self._write_back_P()
-        self.betaidx = self.Nbeta - 1
-        self.beta = self.beta_array[self.betaidx]
-        self.RF = self.RF0 * _alpha_pow(self.alpha, self.beta)
-        if self.verbose:
-            dt = time.time() - t0
-            for j in range(nb):
-                k = k0 + j
-                print('Step %d of %d  beta = %d  RF = %.8e  exit flag = %s  iterations = %s  A = %s'
-                      % (k + 1, self.Nbeta, self.beta_array[k],
-                         float(np.ravel(self.RF0)[0]) * self._rf_scale[k],
-                         self._view(self._flags)[..., k], self._view(self._nit)[..., k],
-                         self._view(self._A)[..., k]))
-            print("\nLadder of %d steps x %d seed(s): %.3f s, %d action+gradient evaluations"
-                  % (nb, self.B, dt, int(self._nfev[:, k0:].sum())))
+            LadderAnnealer._fused_paths(self, k0, mp)
+        else:                                         # full [X | P] rows
+            self._mp[:, k0:] = mp
 
-    # ------------------------------------------------------------------ S1 evaluator
-    def _eval(self, XP, want_grad):
-        XP = np.asarray(XP, dtype=np.float64)
-        single = XP.ndim == 1
-        X2 = np.tile(XP, (self.B, 1)) if single else XP
-        rf = float(self._rf_scale[self.betaidx])
-        A, me, fe, g = self._pb.action_grad(X2, rf, want_grad=want_grad)
-        if single:
-            return A[0], me[0], fe[0], (g[0] if want_grad else None)
-        return A, me, fe, g
-
-    def A_gaussian(self, XP):
-        return self._eval(XP, False)[0]
-
-    A = A_gaussian
+    def _fused_summary(self, k0, dt):
+        for k in range(k0, self.Nbeta):
+            print('Step %d of %d  beta = %d  RF = %.8e  exit flag = %s  iterations = %s  A = %s'
+                  % (k + 1, self.Nbeta, self.beta_array[k],
+                     float(np.ravel(self.RF0)[0]) * self._rf_scale[k],
+                     self._view(self._flags)[..., k], self._view(self._nit)[..., k],
+                     self._view(self._A)[..., k]))
+        print('')
+        LadderAnnealer._fused_summary(self, k0, dt)
 
     def me_gaussian(self, X):
         """Measurement error of a path (va_ode.py:138-158); X may omit the parameters."""
         X = np.asarray(X, dtype=np.float64)
-        ND = self.N_model * self.D
-        if X.shape[-1] == ND:
+        if X.shape[-1] == self._NX:
             pad = self._Pfull[:, self._estpos] if X.ndim == 2 else self._Pfull[0, self._estpos]
             X = np.concatenate([X, pad], axis=-1)
         return self._eval(X, False)[1]
-
-    def fe_gaussian(self, XP):
-        return self._eval(XP, False)[2]
-
-    def _minimize_scipy(self, XP0, rf):
-        """bounds / NCG / TNC: SciPy on the host exactly as _autodiffmin.py:72-146 calls it,
-        with the device kernel in the role of A_gradA_taped."""
-        import scipy.optimize as opt
-        meth = {'L-BFGS-B': 'L-BFGS-B', 'NCG': 'CG', 'TNC': 'TNC'}[self.method]
-
-        def fg(z):
-            A, me, fe, g = self._pb.action_grad(z[None, :], rf)
-            return A[0], g[0]
-        kw = dict(method=meth, jac=True, options=self.opt_args)
-        if meth != 'CG':
-            kw["bounds"] = self.bounds
-        res = opt.minimize(fg, XP0[0], **kw)
-        A, me, fe, _ = self._pb.action_grad(res.x[None, :], rf, want_grad=False)
-        return (res.x[None, :], np.array([res.fun]), me, fe, np.array([res.status]),
-                np.array([res.nit]), np.array([res.nfev]), res.message)
 
     # ------------------------------------------------------------------ savers (va_ode.py:794-889)
     def save_paths(self, filename, dtype=np.float64, fmt="%.8e"):
         ND = self.N_model * self.D
         sav = np.reshape(self._mp[:, :, :ND], (self.B, self.Nbeta, self.N_model, self.D))
         ts = np.resize(np.reshape(self.t_model, (self.N_model, 1)), (self.B, self.Nbeta, self.N_model, 1))
-        sav = np.concatenate((ts, sav), axis=3)
-        sav = sav if self._batched else sav[0]
-        if filename.endswith('.npy'):
-            np.save(filename, sav.astype(dtype))
-        else:
-            np.savetxt(filename, sav.reshape(-1, self.D + 1), fmt=fmt)
+        self._save_array(filename, self._view(np.concatenate((ts, sav), axis=3)), dtype, fmt, self.D + 1)
 
     def save_params(self, filename, dtype=np.float64, fmt="%.8e"):
         if self.NPest == 0:
@@ -554,23 +390,7 @@ class Annealer(HIPmin):
         sav = self._mp[:, :, ND:]
         if self._tdp:                                 # (Nbeta, N_model, NP), va_ode.py:824-840
             sav = sav.reshape(self.B, self.Nbeta, self.N_model, self.NP)
-        sav = sav if self._batched else sav[0]
-        if filename.endswith('.npy'):
-            np.save(filename, sav.astype(dtype))
-        else:
-            np.savetxt(filename, sav.reshape(-1, self.NP), fmt=fmt)
-
-    def save_action_errors(self, filename, cmpt=0, dtype=np.float64, fmt="%.8e"):
-        sav = np.zeros((self.B, self.Nbeta, 5))
-        sav[:, :, 0] = self.beta_array
-        sav[:, :, 1] = self._A; sav[:, :, 2] = self._me; sav[:, :, 3] = self._fe
-        rf0 = float(np.ravel(self.RF0)[0])            # RF0[0, 0] for array-valued RF0 (va_ode.py:861)
-        sav[:, :, 4] = self._fe / (rf0 * _alpha_pow(self.alpha, self.beta_array))
-        sav = sav if self._batched else sav[0]
-        if filename.endswith('.npy'):
-            np.save(filename, sav.astype(dtype))
-        else:
-            np.savetxt(filename, sav.reshape(-1, 5), fmt=fmt)
+        self._save_array(filename, self._view(sav), dtype, fmt, self.NP)
 
     def save_as_minAone(self, savedir='', savefile=None, seed=0):
         """minAone-style text rows [beta, exitflag, A, path..., params...] (va_ode.py:875-889).
@@ -585,12 +405,3 @@ class Annealer(HIPmin):
         exitR = self._flags[seed].reshape((self.Nbeta, 1))
         AR = self._A[seed].reshape((self.Nbeta, 1))
         np.savetxt(savefile, np.hstack((betaR, exitR, AR, self._mp[seed])))
-
-    def gen_xtrace(self):
-        """kept for API compatibility (va_ode.py:894-905); nothing is taped here"""
-        return np.random.rand(self._mp.shape[-1] - (self._Pfull.shape[1] - len(self._estpos)))
-
-    def close(self):
-        if self._pb is not None:
-            self._pb.close()
-            self._pb = None
