@@ -1,6 +1,7 @@
 """Where the stragglers of the C3 evaluation run (profiling only; stamps build: python -m varanneal_amd._build --stamps).
 Per workgroup of k_eval4: start / image landed / rows done / gather done / past the barrier (wall_clock64, 100 MHz) with the
-XCD, shader engine, CU and wave slot it ran on, its dispatch rank on that CU, its seed and tile."""
+XCD, shader engine, CU and wave slot it ran on, its dispatch rank on that CU, its seed and tile; the publishing wave (wave 0)
+against its siblings, up to the acknowledgement of every wave's gradient stores."""
 import os
 import sys
 
@@ -61,4 +62,11 @@ for rep in range(4):
     # waves of one workgroup: spread of rows-done inside a workgroup
     print("   inside a workgroup: rows done of its slowest wave minus its fastest: median %.2f max %.2f us" % (
         np.median(us[:, :, 3].max(axis=1) - us[:, :, 3].min(axis=1)), (us[:, :, 3].max(axis=1) - us[:, :, 3].min(axis=1)).max()))
+    # wave 0 publishes the workgroup's row: do ITS gradient stores end the workgroup?  (slot 5 sums in LDS, 6 past the barrier, 7 stores acknowledged)
+    ack = us[:, :, 7]
+    late = ack[:, 0] - ack[:, 1:].max(axis=1)
+    print("   publishing wave: sums in LDS median %.2f, past the barrier median %.2f; gather done: publisher %.2f others %.2f"
+          % (np.median(us[:, :, 5]), np.median(us[:, :, 6]), np.median(us[:, 0, 4]), np.median(us[:, 1:, 4])))
+    print("   stores acknowledged: workgroup's last wave median %.2f p90 %.2f max %.2f; publisher minus the last of its siblings: median %+.2f p90 %+.2f; it is the workgroup's last in %d of %d"
+          % (np.median(ack.max(axis=1)), np.percentile(ack.max(axis=1), 90), ack.max(), np.median(late), np.percentile(late, 90), int((late >= 0).sum()), nwg))
 pb.close()

@@ -275,12 +275,16 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
                     st_sc1(vrow + e, ((r0 + r1) + r2) + r3);
                 }
             }
-            if (dv.epi != EPI_NONE) {
-                // the wave has nothing else in flight: the row is acknowledged quickly, and the count
-                // is on its way while the wave goes on (gather phase / gradient stores)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == 0) old = __hip_atomic_fetch_add(dv.cnt_eval + (size_t)b * CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+        }
+    };
+    // Wave 0 then counts the workgroup's arrival once the row is acknowledged.  After a plain evaluation's publish() it
+    // first runs its gather phase, which needs no memory: waiting for the acknowledgement right away kept it 0.7 us behind
+    // its siblings, and its gradient stores are the workgroup's last (profiles/r05_publish_c3.txt).  The count is then on
+    // its way while the wave stores its gradient.
+    auto count = [&]() {
+        if (wave == 0 && dv.epi != EPI_NONE) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (lane == 0) old = __hip_atomic_fetch_add(dv.cnt_eval + (size_t)b * CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
 #pragma unroll
@@ -297,7 +301,7 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
         // A plain S1 evaluation needs A = me + fe and dA/dp from the sums: all known once the rows are
         // done.  The row goes out now, and the three dependent round trips of the tail (row
         // acknowledged, arrival counted, rows of the seed read back) run beside the gather phase and
-        // the gradient stores instead of after them.
+        // the gradient stores instead of after them: the acknowledgement travels under the gather phase.
         if (!lsq && s == SUB - 1) publish();
 #pragma unroll
         for (int k = 0; k < K; ++k) gvv[s][k] = 0.0;
@@ -310,11 +314,12 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
                 else tile4_grad<RHS, DISC, K, false, DC, WS, false>(dm, g, t, rg[s], acc, gvv[s]);
             }
         }
+        if (!lsq && s == SUB - 1) count();
         if (s + 1 < SUB) wave_sync_lds();     // the next sub-tile overwrites the product arrays
     }
     VA_E4_STAMP(4);
     // a line-search evaluation also needs g.d, g.g and max|g|: its row waits for the gradient
-    if (lsq) publish();
+    if (lsq) { publish(); count(); }
     {
         // Gradient stores.  The wave's RW*K rows are ONE contiguous run of the path in memory: the values go
         // through the wave's (now dead) product arrays in row-major order and leave as consecutive 16-byte pieces,
@@ -351,12 +356,12 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
     // The last workgroup of the seed runs the tail (and resets the counter for the next launch).
     // (Measured at C3: running it before wave 0's own gradient stores, so that its loads do not retire
     // behind seven write-through stores, is slower -- 10.2 vs 9.6 us: those stores then end the kernel.)
+    VA_E4_STAMP_ACK();
     bool last = false;
     if (wave == 0 && dv.epi != EPI_NONE) {
         old = __builtin_amdgcn_readfirstlane(old);
         asm volatile("" ::: "memory");
         last = old == (unsigned)dm.ntiles - 1u;
-        VA_E4_STAMP(7);
         if (last) {
             if (lane == 0) __hip_atomic_store(dv.cnt_eval + (size_t)b * CNT_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             eval_epilogue<true, (NCV > 0)>(dv, b, lane, reinterpret_cast<SeedHot *>(xsw), dv.epi);

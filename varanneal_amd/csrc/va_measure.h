@@ -4,7 +4,7 @@
 // from the kernels in round 4: their results are kept in profiles/r03_ablation_c3.txt, r03_e5_experiments.txt and
 // r03_nnet_c5x_ablation.txt.
 //   VA_STAMPS      k_eval4: per-wave wall_clock64 (100 MHz) stamps + HW_REG_HW_ID / HW_REG_XCC_ID into the update-partials
-//                  table (tools/timeline.py, tools/timeline2.py)
+//                  table (tools/timeline.py, tools/timeline2.py); slot 7: the wave's gradient stores are acknowledged
 //   VA_PZ_STAMPS   k_seed: thread 0 of workgroup 0 of seed 0 accumulates the ticks between consecutive marks of the cycle
 //                  into pz.stamps (tools/persist_probe.py)
 #pragma once
@@ -18,7 +18,9 @@
     }
 #define VA_E4_STAMP(i) do { if ((threadIdx.x & 63) == 0) tl[i] = wall_clock64(); } while (0)
 #define VA_E4_STAMP_TAIL(last) do { if (last) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tl[1] = wall_clock64(); } } while (0)
+#define VA_E4_STAMP_ACK() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if ((threadIdx.x & 63) == 0) tl[7] = wall_clock64(); } while (0)
 #else
+#define VA_E4_STAMP_ACK() do { } while (0)
 #define VA_E4_STAMP_SETUP(dv, w)
 #define VA_E4_STAMP(i) do { } while (0)
 #define VA_E4_STAMP_TAIL(last) do { } while (0)
