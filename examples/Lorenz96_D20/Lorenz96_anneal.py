@@ -3,9 +3,11 @@
 Counterpart of the reference's examples/Lorenz96_D20/Lorenz96_anneal.py (SURVEY.md
 8(a) row H): same model, hyper-parameters, call order and output files; the only
 edits are the import (varanneal_amd instead of varanneal), an explicit RNG seed, and
-the data file location.  Optional: --seeds B runs B random initial paths as one batch.
+the data file location.  Optional: --seeds B runs B random initial paths as one batch;
+--predict N holds the last N observations back from the fit, integrates the model N steps on
+from every rung's estimate (Annealer.predict) and prints the forecast's RMS error per rung.
 
-    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite]
+    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40]
 """
 import argparse
 import os
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--disc", default="SimpsonHermite")
     ap.add_argument("--rng", type=int, default=12345)
     ap.add_argument("--out", default=".")
+    ap.add_argument("--predict", type=int, default=0, metavar="N",
+                    help="hold the last N observations back and report the forecast error per rung")
     args = ap.parse_args()
 
     D = 20
@@ -48,6 +52,14 @@ def main():
     dt_data = times_data[1] - times_data[0]
     N_data = len(times_data)
     data = data[:, 1:][:, Lidx]
+    held_back = None
+    if args.predict > 0:
+        # fit what comes before the last N rows (Simpson-Hermite needs an odd number of them); the last fitted row is
+        # row 0 of what the forecast is compared with
+        n_fit = N_data - args.predict
+        first = 1 if (args.disc == "SimpsonHermite" and n_fit % 2 == 0) else 0
+        held_back = data[n_fit - 1:]
+        data, times_data, N_data = data[first:n_fit], times_data[first:n_fit], n_fit - first
 
     # Initial path/parameter guesses (reference lines 49-68)
     dt_model = dt_data
@@ -72,6 +84,12 @@ def main():
                    opt_args=BFGS_options, adolcID=0)
     print("\nHIP annealing completed in %f s." % (time.time() - tstart))
     print("estimated forcing k (true value 8.17): %s" % np.ravel(anneal1.P))
+
+    if held_back is not None:
+        err = anneal1.prediction_error(held_back)          # (nbeta,), or (seeds, nbeta)
+        print("\nforecast of %d steps from every rung's estimate: RMS error on the measured components" % args.predict)
+        for k, beta in enumerate(beta_array):
+            print("beta = %3d   %s" % (beta, np.array2string(np.atleast_1d(err[..., k]), precision=4)))
 
     anneal1.save_paths(os.path.join(args.out, "paths.npy"))
     anneal1.save_params(os.path.join(args.out, "params.npy"))

@@ -201,6 +201,19 @@ int va_anneal(va_handle h, double *XP_inout, int64_t ld, int32_t mem, const doub
  * out[N_model*D + NP] HOST. */
 int va_get_minpath(va_handle h, int32_t seed, int32_t beta_idx, double *out);
 
+/* Forecast from estimated states: integrate T trajectories of the handle's model forward with classical RK4 at the fixed
+ * step dt_model / substeps (csrc/va_predict.h; the reference leaves this to the user's script).
+ *   x0 [T*D], p [T*NP] (full parameter vectors, constant over the forecast), HOST
+ *   stim NULL, or [(n_steps+1)*n_stim] HOST: the stimulus at the model-step times t0 + n dt_model, shared by all
+ *        trajectories, interpolated linearly at the stage times in between
+ *   out [T*n_out*D] HOST, n_out = n_steps / every + 1: model steps 0, every, 2 every, ...; row 0 is x0 itself
+ * The model, D, NP, n_stim, dt_model, device and stream are the handle's.  Not tied to the stored minpaths (the caller
+ * chooses the states to start from), and the handle's resident paths, seed states and captured graphs are left alone.
+ * VA_EINVAL: T, n_steps, substeps or every < 1; stim missing on a model with a stimulus, or given to one without.
+ * VA_EUNSUPPORTED: network handles; D > 1024; a generated model without a flat form (more than 128 parameters). */
+int va_predict(va_handle h, const double *x0, const double *p, int32_t T, double t0,
+               int32_t n_steps, int32_t substeps, int32_t every, const double *stim, double *out);
+
 /* Measurement hook for bench.py: `iters` complete S1 evaluations (the same launch va_action_grad
  * makes: A, me, fe and the full gradient are formed every time) on the resident paths (those of
  * the last va_action_grad / va_anneal call), bracketed by HIP events on the handle's stream;

@@ -204,6 +204,7 @@ def lib():
     L.va_anneal.argtypes = [h, C.c_void_p, C.c_int64, C.c_int32, c_dp, C.c_int32,
                             C.POINTER(LbfgsOpts), c_dp, c_dp, c_ip, c_ip, c_lp, c_dp]
     L.va_get_minpath.argtypes = [h, C.c_int32, C.c_int32, c_dp]
+    L.va_predict.argtypes = [h, c_dp, c_dp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp]
     L.va_eval_timed.argtypes = [h, C.c_double, C.c_int32, C.POINTER(C.c_float)]
     L.va_eval_timed_prepare.argtypes = [h, C.c_double, C.c_int32]
     L.va_get_counters.argtypes = [h, c_lp, c_lp, c_lp]
@@ -224,7 +225,7 @@ def lib():
     L.va_problem_persistent.restype = C.c_int
     for fn in ("va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_tune", "va_problem_create", "va_nnet_problem_create",
                "va_problem_info", "va_action_grad",
-               "va_minimize_lbfgs", "va_anneal", "va_get_minpath", "va_eval_timed", "va_eval_timed_prepare",
+               "va_minimize_lbfgs", "va_anneal", "va_get_minpath", "va_predict", "va_eval_timed", "va_eval_timed_prepare",
                "va_get_counters", "va_debug_read_partials", "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed",
                "va_comm_unique_id", "va_comm_create", "va_gather_results"):
         getattr(L, fn).restype = C.c_int
@@ -234,7 +235,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -438,6 +439,32 @@ class Problem(object):
                                 nfev.ctypes.data_as(c_lp), mp.ctypes.data_as(c_dp) if want_paths else None))
         return dict(x=XP if xp_device is None else None, A=ame[:, :, 0], me=ame[:, :, 1],
                     fe=ame[:, :, 2], pest=pest, status=st, nit=nit, nfev=nfev, minpaths=mp)
+
+    def predict(self, x0, p, n_steps, t0=0.0, substeps=1, every=1, stim=None):
+        """Integrate the model forward from the T states x0 (T, D) with the full parameter vectors p (T, NP): classical
+        RK4 at the fixed step dt_model / substeps on the device (va_predict).  stim: (n_steps + 1, n_stim), the stimulus at
+        the model-step times from t0 on (models with a stimulus only).  Returns (T, n_steps // every + 1, D): the model
+        steps 0, every, 2 every, ...; row 0 is x0."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("predict: a network handle has no differential equation to integrate")
+        D, NP = self.desc.D, self.desc.NP
+        x0 = _f64(x0).reshape(-1, D)
+        T = x0.shape[0]
+        p = _f64(p).reshape(-1, NP) if NP else np.zeros((T, 0))
+        if p.shape[0] == 1 and T > 1:
+            p = np.ascontiguousarray(np.broadcast_to(p, (T, NP)))
+        if p.shape[0] != T:
+            raise ValueError("predict: %d states but %d parameter vectors" % (T, p.shape[0]))
+        n_steps, substeps, every = int(n_steps), int(substeps), int(every)
+        st = None
+        if stim is not None:
+            st = _f64(stim).reshape(max(n_steps, 0) + 1, -1)
+            if st.shape[1] != self.desc.n_stim and self.desc.n_stim:
+                raise ValueError("predict: the stimulus must have %d rows of %d column(s)" % (n_steps + 1, self.desc.n_stim))
+        out = np.empty((T, n_steps // every + 1 if every >= 1 and n_steps >= 1 else 1, D))
+        check(self._L.va_predict(self._h, x0.ctypes.data_as(c_dp), p.ctypes.data_as(c_dp), T, float(t0), n_steps, substeps,
+                                 every, st.ctypes.data_as(c_dp) if st is not None else None, out.ctypes.data_as(c_dp)))
+        return out
 
     def eval_timed_prepare(self, rf_scale, iters):
         """arm the seeds and build / upload the hipGraph eval_timed(rf_scale, iters) replays (nothing timed)"""

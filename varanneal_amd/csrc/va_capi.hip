@@ -37,6 +37,7 @@
 #include "va_nnet.h"
 #include "va_eval_flat.h"
 #include "va_persist.h"
+#include "va_predict.h"
 
 using namespace va;
 
@@ -81,6 +82,7 @@ struct UserRhs {
     void (*launch)(const Dev *, void *) = nullptr;
     int (*prepare)(const Dev *) = nullptr;
     int (*seed_kernel)(const Dev *, int, void *) = nullptr;      // the persistent per-seed ladder kernel (va_persist.h), if the module carries it
+    int (*predict)(const PredictArgs *, int, void *) = nullptr;  // the RK4 predictor (va_predict.h): modules with a flat struct
     int NP = 0, D = 0, NSTIM = 0;
     // variant.n_colp_vectors > 0: the column-run instantiation is of the model's column-parameter form (RhsUserColP); its map
     // (va_user_colp_map): shared scalars S, vectors V, then the global index of each shared scalar and of each vector entry
@@ -103,6 +105,8 @@ struct va_problem_s {
     void (*user_launch)(const Dev *, void *) = nullptr;
     int (*user_prepare)(const Dev *) = nullptr;
     int (*user_seed)(const Dev *, int, void *) = nullptr;
+    int (*user_predict)(const PredictArgs *, int, void *) = nullptr;
+    bool user_rhs = false;             // the right-hand side is a generated module's
     NnetActLaunch user_act = nullptr;  // generated activation module's launcher (nn.act >= NNET_USER)
     // few seeds, short paths: the whole ladder in ONE launch, every vector of the minimisation resident in
     // the LDS of pz_G workgroups per seed (va_persist.h); chosen at create when the slices fit and all are co-resident
@@ -603,6 +607,7 @@ int plan_problem(va_handle h, const va_problem_desc *d, const UserRhs *user, Eva
     h->user_launch = mp.variant ? user->launch_var : user->launch;
     h->user_prepare = mp.variant ? user->prepare_var : user->prepare;
     h->user_seed = user->seed_kernel;
+    h->user_predict = user->predict; h->user_rhs = true;
     dv.dm.lin = user->variant.has_linear;
     dv.cps = mp.cps; dv.cpv = mp.cpv;
     dv.cpnsg = (mp.cpv && plan.emode == 5) ? plan.g5.NSG : 0;
@@ -951,6 +956,7 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
     u.launch = (void (*)(const Dev *, void *))dlsym(u.dl, "va_user_launch_eval");
     u.prepare = (int (*)(const Dev *))dlsym(u.dl, "va_user_prepare_eval");
     u.seed_kernel = (int (*)(const Dev *, int, void *))dlsym(u.dl, "va_user_seed_kernel");
+    u.predict = (int (*)(const PredictArgs *, int, void *))dlsym(u.dl, "va_user_predict");       // (optional: no flat struct, no predictor)
     if (!info || !u.launch || !u.prepare) { dlclose(u.dl); return fail(VA_EINVAL, "%s lacks va_user_rhs_info / va_user_launch_eval / va_user_prepare_eval", path); }
     int ri[5] = {0, 0, 0, 0, 0};           // (NP, D, NSTIM, sizeof(Dev), sizeof(SeedState))
     info(ri);
@@ -1166,6 +1172,51 @@ int va_minimize_lbfgs(va_handle h, double *XP, int64_t ld, int32_t mem, double r
         if (me) me[b] = ame[3 * b + 1];
         if (fe) fe[b] = ame[3 * b + 2];
     }
+    return VA_OK;
+}
+
+// Forecast: T trajectories of the handle's model from x0 with the parameters p, classical RK4 (va_predict.h).  Works on
+// buffers of its own: the handle's resident paths, seed states and captured graphs are not touched.
+int va_predict(va_handle h, const double *x0, const double *p, int32_t T, double t0, int32_t n_steps, int32_t substeps,
+               int32_t every, const double *stim, double *out)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    if (!x0 || !p || !out) return fail(VA_EINVAL, "x0 / p / out must not be NULL");
+    if (T < 1 || n_steps < 1 || substeps < 1 || every < 1)
+        return fail(VA_EINVAL, "T, n_steps, substeps and every must be at least 1 (T=%d n_steps=%d substeps=%d every=%d)", T, n_steps, substeps, every);
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "a network handle has no differential equation to integrate");
+    const Dims &dm = h->dv.dm;
+    const int nstim = h->dv.pp.nstim;
+    if (nstim > 0 && !stim) return fail(VA_EINVAL, "the model takes a stimulus of %d column(s): pass its %d rows from t0 on", nstim, n_steps + 1);
+    if (nstim == 0 && stim) return fail(VA_EINVAL, "the model takes no stimulus, but one was passed");
+    if (h->user_rhs && !h->user_predict)
+        return fail(VA_EUNSUPPORTED, "the model has no flat form f(x, i, p) for the integrator to call (more than %d parameters: "
+                                     "its module carries the column-parameter form only)", RHS_BIG_NP);
+    if ((int64_t)n_steps * substeps > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_steps x substeps does not fit 32-bit indexing");
+    PredictArgs a;
+    a.T = T; a.D = dm.D; a.NP = dm.NPt; a.nstim = nstim; a.n_steps = n_steps; a.substeps = substeps; a.every = every;
+    a.n_out = n_steps / every + 1; a.t0 = t0; a.dt = dm.dt;
+    if (!plan_predict(a.D, T, a.NP, nstim, a.geo)) return fail(VA_EUNSUPPORTED, "va_predict: D=%d: %s", a.D, a.geo.why);
+    HIPCHK(hipSetDevice(h->device));
+    // one allocation: [x0 | p | stim | out]
+    const size_t nx = (size_t)T * a.D, np = (size_t)T * a.NP, ns = (size_t)(n_steps + 1) * nstim, no = (size_t)T * a.n_out * a.D;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (nx + np + ns + no + 1)));
+    struct Free { double *q; ~Free() { (void)hipFree(q); } } guard{buf};
+    double *x0_d = buf, *p_d = x0_d + nx, *st_d = p_d + np, *out_d = st_d + ns;
+    HIPCHK(hipMemcpyAsync(x0_d, x0, sizeof(double) * nx, hipMemcpyHostToDevice, h->stream));
+    if (np) HIPCHK(hipMemcpyAsync(p_d, p, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+    if (ns) HIPCHK(hipMemcpyAsync(st_d, stim, sizeof(double) * ns, hipMemcpyHostToDevice, h->stream));
+    a.x0 = x0_d; a.p = p_d; a.stim = ns ? st_d : nullptr; a.out = out_d;
+    const hipError_t e = h->user_predict ? (hipError_t)h->user_predict(&a, (int)sizeof(PredictArgs), (void *)h->stream)
+                                         : launch_predict_builtin(a, h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
+        return fail(VA_EHIP, "k_predict launch: %s", hipGetErrorString(e));
+    }
+    HIPCHK(hipMemcpyAsync(out, out_d, sizeof(double) * no, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
     return VA_OK;
 }
 

@@ -25,6 +25,7 @@
 #include "va_eval4.h"
 #include "va_tile5.h"
 #include "va_persist.h"
+#include "va_predict.h"
 
 namespace va {
 
@@ -161,6 +162,9 @@ hipError_t prepare_eval(const Dev &dv, int rhs)
 }
 
 hipError_t seed_kernel_builtin(const Dev &dv, bool launch, hipStream_t s) { return seed_kernel_op<RhsL96>(dv, launch, s); }
+
+// the RK4 predictor (va_predict.h) for the built-in right-hand side: one wave per workgroup for D <= 64, 1 .. 4 columns per lane beyond
+hipError_t launch_predict_builtin(const PredictArgs &a, hipStream_t s) { return launch_predict<RhsL96, 0>(a, s); }
 
 // ------------------------------------------------------------------ K2: tails as kernels of their own
 // (the network action, whose evaluation is several kernels, and grids too large to fold the tail

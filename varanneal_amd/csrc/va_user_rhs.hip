@@ -12,6 +12,7 @@
 #include "va_eval4.h"
 #include "va_eval5.h"
 #include "va_persist.h"
+#include "va_predict.h"
 
 #ifndef VA_USER_RHS_HEADER
 #error "compile with -DVA_USER_RHS_HEADER='\"path/to/generated_header.h\"'"
@@ -58,6 +59,16 @@ int va_user_seed_kernel(const va::Dev *dv, int launch, void *stream)
 {
     return (int)va::seed_kernel_op<va::RhsUser>(*dv, launch != 0, (hipStream_t)stream);
 }
+
+// the RK4 predictor (va_predict.h) for this model: only a module with a flat struct (the generator says so: VA_USER_FLAT)
+// has the f(x_row, i, ...) the integrator calls.  args_bytes: sizeof(PredictArgs) as the caller knows it
+#ifdef VA_USER_FLAT
+int va_user_predict(const va::PredictArgs *a, int args_bytes, void *stream)
+{
+    if (args_bytes != (int)sizeof(va::PredictArgs)) return (int)hipErrorInvalidValue;
+    return (int)va::launch_predict<va::RhsUser, va::RhsUser::D>(*a, (hipStream_t)stream);
+}
+#endif
 
 // Besides the flat kernel a module may carry ONE instantiation of a column-run kernel, named when the module
 // was generated (va_eval_plan; -DVA_USER_EK=3|4 -DVA_USER_DISC -DVA_USER_K -DVA_USER_W):

@@ -367,6 +367,55 @@ class Annealer(LadderAnnealer):
         print('')
         LadderAnnealer._fused_summary(self, k0, dt)
 
+    # ------------------------------------------------------------------ forecast
+    def _select(self, beta, seeds):
+        """(seed indices, rung indices) of a selection: None = all; an int or a sequence of ints otherwise"""
+        def pick(sel, n, what):
+            idx = np.arange(n) if sel is None else np.atleast_1d(np.asarray(sel, dtype=np.intp))
+            if idx.ndim != 1 or np.any(idx < -n) or np.any(idx >= n):
+                raise IndexError("%s selection %r outside [0, %d)" % (what, sel, n))
+            return idx % n
+        if seeds is not None and not self._batched:
+            raise ValueError("seeds= selects from a batch; this run has one seed")
+        return pick(seeds, self.B, "seed"), pick(beta, self.Nbeta, "rung")
+
+    def predict(self, n_steps, beta=None, seeds=None, substeps=1, every=1, stim=None):
+        """Forecast from the estimates (after anneal()): the model integrated n_steps steps of dt_model forward from the
+        LAST row of every selected (seed, rung)'s minimising path, with that rung's full parameter vector (the last row's
+        with time-dependent parameters), t0 = t_model[-1]: classical RK4 at dt_model / substeps, on the device, all
+        selected trajectories in one call.
+          beta / seeds  indices into beta_array / the batch (an int or a sequence); None = all
+          every         keep the model steps 0, every, 2 every, ...: n_out = n_steps // every + 1 rows, row 0 the last fitted state
+          stim          (n_steps + 1, n_stim): the stimulus at t_model[-1] + n dt_model, for models that take one
+        Returns (nbeta_sel, n_out, D), or (B_sel, nbeta_sel, n_out, D) for a batch."""
+        if self._pb is None or not getattr(self, "initalized", False):
+            raise ValueError("predict() works after anneal() / anneal_init()")
+        sb, kb = self._select(beta, seeds)
+        N, D, NP, NX = self.N_model, self.D, self.NP, self._NX
+        rows = self._mp[sb][:, kb]                                   # (B_sel, nbeta_sel, NX + stored parameter block)
+        x0 = rows[:, :, (N - 1) * D:N * D]
+        p = rows[:, :, NX + (N - 1) * NP:NX + N * NP] if self._tdp else rows[:, :, NX:]
+        out = self._pb.predict(x0.reshape(-1, D), p.reshape(-1, NP), n_steps, t0=float(self.t_model[-1]),
+                               substeps=substeps, every=every, stim=stim)
+        out = out.reshape(len(sb), len(kb), out.shape[1], D)
+        return out if self._batched else out[0]
+
+    def prediction_error(self, Y_future, **predict_kwargs):
+        """RMS error of the forecast against held-back observations: Y_future (n_out, L), the Lidx columns at the output
+        times of predict(n_steps = (n_out - 1) * every, ...), row 0 being the last fitted time (not counted).  Per
+        (seed, rung): shape (nbeta_sel,), or (B_sel, nbeta_sel) for a batch."""
+        Yf = np.asarray(Y_future, dtype=np.float64)
+        if Yf.ndim != 2 or Yf.shape[0] < 2 or Yf.shape[1] != self.L:
+            raise ValueError("Y_future must have shape (n_out >= 2, L = %d), got %s" % (self.L, Yf.shape))
+        every = int(predict_kwargs.get("every", 1))
+        if "n_steps" not in predict_kwargs:
+            predict_kwargs = dict(predict_kwargs, n_steps=(Yf.shape[0] - 1) * every)
+        pred = self.predict(**predict_kwargs)
+        if pred.shape[-2] != Yf.shape[0]:
+            raise ValueError("the forecast has %d output rows, Y_future %d" % (pred.shape[-2], Yf.shape[0]))
+        diff = pred[..., 1:, self.Lidx] - Yf[1:]
+        return np.sqrt(np.mean(diff * diff, axis=(-2, -1)))
+
     def me_gaussian(self, X):
         """Measurement error of a path (va_ode.py:138-158); X may omit the parameters."""
         X = np.asarray(X, dtype=np.float64)
