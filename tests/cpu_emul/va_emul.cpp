@@ -55,7 +55,7 @@ int setup(const va_problem_desc *d, int T, Emul &E)
         int K = (T + rows1 - 1) / rows1;
         K = K < 4 ? 4 : (K > 8 ? 8 : K);
         if (m.disc == DISC_SH && (K & 1)) ++K;
-        const char *se = getenv("VA_EMUL_SUB");            // sub-tiles per wave (the device picks 1..3, va_capi.hip)
+        const char *se = getenv("VA_EMUL_SUB");            // sub-tiles per wave (the device kernels are compiled for 1 only, va_eval4.h)
         const int SUB = se ? atoi(se) : 1;
         int ne = RhsL96s::NE;
 #ifdef VA_USER_COL

@@ -91,10 +91,21 @@ def test_module_cross_compiles_for_gfx950(nakl_module):
     assert os.path.exists(nakl_module["so"]) and os.path.getsize(nakl_module["so"]) > 10000
     import ctypes as C
     L = C.CDLL(nakl_module["so"])               # loads without a GPU; exports the module ABI
-    v = (C.c_int * 5)()
-    L.va_user_rhs_info(v)
-    assert list(v)[:3] == [18, 4, 1]
-    assert hasattr(L, "va_user_launch_eval")
+    t = _rhs_table(L)
+    assert [t.NP, t.D, t.NSTIM] == [18, 4, 1]
+    assert t.eval and t.seed and t.predict       # the flat kernel, k_seed and the predictor
+
+
+def _rhs_table(L):
+    """RhsTable (csrc/va_device.h) as a module's one entry point va_user_rhs_table fills it"""
+    import ctypes as C
+
+    class RhsTable(C.Structure):
+        _fields_ = ([(n, C.c_int) for n in ("bytes", "dev_bytes", "seed_bytes", "predict_bytes", "NP", "D", "NSTIM")]
+                    + [(n, C.c_void_p) for n in ("eval", "eval_var", "seed", "predict")])
+    t = RhsTable()
+    assert L.va_user_rhs_table(C.byref(t), C.sizeof(t)) == C.sizeof(t) == t.bytes
+    return t
 
 
 def _golden_nakl():
@@ -221,7 +232,7 @@ def test_column_module_exports_its_variant():
     L = C.CDLL(m["so"])
     v = (C.c_int * 12)()
     L.va_user_variant_info(v)
-    assert list(v)[:6] == [4, 1, 7, 1, 2, 0] and list(v)[10] == 0 and hasattr(L, "va_user_launch_variant") and hasattr(L, "va_user_prepare_variant")
+    assert list(v)[:6] == [4, 1, 7, 1, 2, 0] and list(v)[10] == 0 and _rhs_table(L).eval_var
 
 
 def test_module_without_variant_reports_none(nakl_module):
@@ -229,7 +240,7 @@ def test_module_without_variant_reports_none(nakl_module):
     L0 = C.CDLL(nakl_module["so"])                              # no variant asked for: flat kernel only
     v = (C.c_int * 12)()
     L0.va_user_variant_info(v)
-    assert list(v)[0] == 0 and not hasattr(L0, "va_user_launch_variant")
+    assert list(v)[0] == 0 and not _rhs_table(L0).eval_var
 
 
 def test_eval_plan_matches_the_geometry_rules():

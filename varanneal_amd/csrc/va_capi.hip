@@ -75,15 +75,9 @@ int fail(int code, const char *fmt, ...)
 // generated right-hand-side modules (va_rhs_load_module); ids are VA_RHS_USER_BASE + index
 struct UserRhs {
     ModuleVariant variant;     // the ONE column-run instantiation the module carries besides its flat kernel, if any (va_user_rhs.hip)
-    void (*launch_var)(const Dev *, void *) = nullptr;
-    int (*prepare_var)(const Dev *) = nullptr;
     std::string path;
     void *dl = nullptr;
-    void (*launch)(const Dev *, void *) = nullptr;
-    int (*prepare)(const Dev *) = nullptr;
-    int (*seed_kernel)(const Dev *, int, void *) = nullptr;      // the persistent per-seed ladder kernel (va_persist.h), if the module carries it
-    int (*predict)(const PredictArgs *, int, void *) = nullptr;  // the RK4 predictor (va_predict.h): modules with a flat struct
-    int NP = 0, D = 0, NSTIM = 0;
+    RhsTable table = {};       // the module's launchers and sizes (va_user_rhs_table)
     // variant.n_colp_vectors > 0: the column-run instantiation is of the model's column-parameter form (RhsUserColP); its map
     // (va_user_colp_map): shared scalars S, vectors V, then the global index of each shared scalar and of each vector entry
     std::vector<int> colp;
@@ -102,12 +96,8 @@ std::mutex g_user_rhs_mutex;            // the registry is process-wide; handles
 struct va_problem_s {
     Dev dv;
     int device = 0, rhs = 0, keep_paths = 0;
-    void (*user_launch)(const Dev *, void *) = nullptr;
-    int (*user_prepare)(const Dev *) = nullptr;
-    int (*user_seed)(const Dev *, int, void *) = nullptr;
-    int (*user_predict)(const PredictArgs *, int, void *) = nullptr;
-    bool user_rhs = false;             // the right-hand side is a generated module's
-    NnetActLaunch user_act = nullptr;  // generated activation module's launcher (nn.act >= NNET_USER)
+    RhsTable rt = {};                  // the right-hand side's launchers (a copy; eval: the kernel THIS handle runs)
+    NnetActLaunch nn_act = nullptr;    // generated activation module's launcher (nn.act >= NNET_USER)
     // few seeds, short paths: the whole ladder in ONE launch, every vector of the minimisation resident in
     // the LDS of pz_G workgroups per seed (va_persist.h); chosen at create when the slices fit and all are co-resident
     bool persist = false, tune_persist = true;
@@ -166,21 +156,20 @@ void run_eval(va_handle h, int epi)
 {
     if (epi != EPI_FINALIZE) h->timed_armed_rf = -1.0;      // (line-search launches move the seeds' states)
     h->dv.lsrun = epi == EPI_LS ? 1 : 0;       // (S1 evaluations put every seed in PH_START: no line-search points)
+    EvalOp op{false, h->stream, hipSuccess};
     if (h->is_nnet ? !h->nn.small : !h->fold) {
         // (large grids: a workgroup that waits for its arrival to come back holds its LDS and wave
         // slots ~1 us longer, which costs more than the 64-wave tail kernel it saves)
         h->dv.epi = EPI_NONE;
-        if (h->is_nnet) launch_nnet_eval(h->dv, h->nn, h->stream, h->user_act);
-        else if (h->user_launch) h->user_launch(&h->dv, (void *)h->stream);
-        else launch_eval(h->dv, h->rhs, h->stream);
+        if (h->is_nnet) launch_nnet_eval(h->dv, h->nn, h->stream, h->nn_act);
+        else h->rt.eval(h->dv, op);
         if (epi == EPI_FINALIZE) launch_finalize_eval(h->dv, h->stream);
         else if (epi == EPI_LS) launch_ls(h->dv, h->stream);
         return;
     }
     h->dv.epi = epi;
-    if (h->is_nnet) { launch_nnet_eval(h->dv, h->nn, h->stream, h->user_act); return; }   // (small nets: k_nnet_small carries the tail)
-    if (h->user_launch) h->user_launch(&h->dv, (void *)h->stream);
-    else launch_eval(h->dv, h->rhs, h->stream);
+    if (h->is_nnet) { launch_nnet_eval(h->dv, h->nn, h->stream, h->nn_act); return; }   // (small nets: k_nnet_small carries the tail)
+    h->rt.eval(h->dv, op);
 }
 
 // per-seed vectors, L-BFGS history, partial tables and result tables: the part of the device
@@ -415,8 +404,9 @@ int run_ladder_persist(va_handle h, const double *rf_scale, int nbeta, bool *fel
     HIPCHK(hipMemsetAsync(dv.pz.xch, 0, h->pz_xch_bytes, h->stream));           // (tags restart at 1 with every launch)
     HIPCHK(hipMemsetAsync(h->pz_misc, 0, 16, h->stream));
     TRY(arm_ladder(h, rf_scale, nbeta, false));
-    const hipError_t e = h->user_seed ? (hipError_t)h->user_seed(&dvp, 1, (void *)h->stream) : seed_kernel_builtin(dvp, true, h->stream);
-    if (e != hipSuccess) {
+    EvalOp op{false, h->stream, hipSuccess};
+    h->rt.seed(dvp, op);
+    if (op.err != hipSuccess) {
         (void)hipGetLastError();
         h->persist = false;           // (for the rest of this handle's life)
         *fell_back = true;
@@ -545,9 +535,10 @@ int validate_desc(const va_problem_desc *d, UserRhs &user_copy, const UserRhs **
         if ((size_t)(d->rhs - VA_RHS_USER_BASE) >= g_user_rhs.size()) return fail(VA_EINVAL, "rhs module id %d was never registered", d->rhs);
         user_copy = g_user_rhs[d->rhs - VA_RHS_USER_BASE];
         *user = &user_copy;
-        if (user_copy.NP != d->NP || user_copy.D != d->D || user_copy.NSTIM != d->n_stim)
+        const RhsTable &t = user_copy.table;
+        if (t.NP != d->NP || t.D != d->D || t.NSTIM != d->n_stim)
             return fail(VA_EINVAL, "rhs module %s was generated for D=%d NP=%d n_stim=%d, problem has D=%d NP=%d n_stim=%d",
-                        user_copy.path.c_str(), user_copy.D, user_copy.NP, user_copy.NSTIM, d->D, d->NP, d->n_stim);
+                        user_copy.path.c_str(), t.D, t.NP, t.NSTIM, d->D, d->NP, d->n_stim);
     } else if (d->rhs != VA_RHS_LORENZ96) return fail(VA_EUNSUPPORTED, "unknown built-in rhs %d", d->rhs);
     if (d->rhs == VA_RHS_LORENZ96 && (d->NP != RhsL96::NP || d->D < 4))
         return fail(VA_EINVAL, "Lorenz-96 needs NP=1 and D>=4 (NP=%d D=%d)", d->NP, d->D);
@@ -595,6 +586,7 @@ int plan_problem(va_handle h, const va_problem_desc *d, const UserRhs *user, Eva
     Dev &dv = h->dv;
     h->rhs = d->rhs;
     if (!user) {
+        builtin_rhs_table(h->rt);
         EvalForm l96;
         l96.ne = RhsL96s::NE; l96.ghost = RhsL96g::GHOST; l96.has_reach5 = true;
         l96.reach5[0] = t5_xl<RhsL96s>(); l96.reach5[1] = t5_xr<RhsL96s>(); l96.reach5[2] = t5_gl<RhsL96s>(); l96.reach5[3] = t5_gr<RhsL96s>();
@@ -604,10 +596,8 @@ int plan_problem(va_handle h, const va_problem_desc *d, const UserRhs *user, Eva
     ModulePlan mp;
     TRY(plan_module(d, *user, mp));
     plan = mp.plan;
-    h->user_launch = mp.variant ? user->launch_var : user->launch;
-    h->user_prepare = mp.variant ? user->prepare_var : user->prepare;
-    h->user_seed = user->seed_kernel;
-    h->user_predict = user->predict; h->user_rhs = true;
+    h->rt = user->table;
+    if (mp.variant) h->rt.eval = user->table.eval_var;
     dv.dm.lin = user->variant.has_linear;
     dv.cps = mp.cps; dv.cpv = mp.cpv;
     dv.cpnsg = (mp.cpv && plan.emode == 5) ? plan.g5.NSG : 0;
@@ -661,7 +651,9 @@ int prepare_kernels(va_handle h)
     if (need > cap)
         return fail(VA_EUNSUPPORTED, "a tile of %d rows x D=%d needs %zu B of LDS (> %zu): state too wide for this kernel",
                     dm.T, dm.D, need, cap);
-    hipError_t e = h->user_prepare ? (hipError_t)h->user_prepare(&dv) : prepare_eval(dv, h->rhs);
+    EvalOp op{true, nullptr, hipSuccess};
+    h->rt.eval(dv, op);
+    hipError_t e = op.err;
     if (e == hipSuccess && dm.bounded) e = prepare_lbfgsb(dv);
     if (e != hipSuccess) return fail(VA_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
     return VA_OK;
@@ -788,20 +780,21 @@ int upload_problem_data(va_handle h, const va_problem_desc *d, const UserRhs *us
 // Step 6: few seeds, short paths: can the whole minimisation live in LDS?  (flat tile phases: any right-hand side, any
 // discretisation, weight arrays, merr_nskip, full weight matrices; not bounds, time-dependent parameters, a dense
 // linear part, more than RHS_MAX_NP parameters, or the padded observation rows of the streaming kernel)
-int choose_persist(va_handle h, const va_problem_desc *d, const UserRhs *user)
+int choose_persist(va_handle h, const va_problem_desc *d)
 {
     Dev &dv = h->dv;
     const Dims &dm = dv.dm;
     const size_t B = dm.B;
-    if (dm.bounded || dm.tdp || dm.lin || d->NP > RHS_MAX_NP || dm.emode == 5 || (user && !user->seed_kernel)) return VA_OK;
+    if (dm.bounded || dm.tdp || dm.lin || d->NP > RHS_MAX_NP || dm.emode == 5 || !h->rt.seed) return VA_OK;
     int G = 0, T = 0, ncu = 0;
     HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d->device));
     h->pz_maxG = ncu / (int)B;
     if (h->pz_maxG < 1 || !persist_geometry(dm.N, dm.D, dm.L, dm.NP, dm.NPest, dm.m, dm.disc, PZ_LDS_BYTES, h->pz_maxG, 0, &G, &T)) return VA_OK;
     Dev dvp = dv;
     dvp.dm.T = T; dvp.dm.ntiles = G;
-    const hipError_t e = h->user_seed ? (hipError_t)h->user_seed(&dvp, 0, nullptr) : seed_kernel_builtin(dvp, false, nullptr);
-    if (e != hipSuccess) { (void)hipGetLastError(); return VA_OK; }
+    EvalOp op{true, nullptr, hipSuccess};
+    h->rt.seed(dvp, op);
+    if (op.err != hipSuccess) { (void)hipGetLastError(); return VA_OK; }
     h->persist = true; h->pz_G = G; h->pz_T = T;
     // (sized for the most workgroups a seed may get: va_problem_tune may choose other slices)
     const size_t units = B * 2 * (size_t)h->pz_maxG * (size_t)pz_row_granules(dm.D) * 2;     // 8-byte units: 16 per granule pair
@@ -899,7 +892,7 @@ int create_nnet_image(va_handle h, const va_nnet_desc *d, const NnetPlan &p)
         nn.rmm_in = ri; nn.rmm_out = ro; nn.lidx_in = li; nn.lidx_out = lo;
     }
     if (p.fb_ok) {
-        const hipError_t e = prepare_nnet_fb(nn, h->user_act);
+        const hipError_t e = prepare_nnet_fb(nn, h->nn_act);
         if (e != hipSuccess) { (void)hipGetLastError(); nn.Wf = nullptr; }      // (the tune knob then refuses)
     }
     return VA_OK;
@@ -952,40 +945,35 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
     u.dl = dlopen(path, RTLD_NOW | RTLD_LOCAL);
     if (!u.dl) return fail(VA_EINVAL, "dlopen(%s): %s", path, dlerror());
     typedef void (*info_fn)(int *);
-    info_fn info = (info_fn)dlsym(u.dl, "va_user_rhs_info");
-    u.launch = (void (*)(const Dev *, void *))dlsym(u.dl, "va_user_launch_eval");
-    u.prepare = (int (*)(const Dev *))dlsym(u.dl, "va_user_prepare_eval");
-    u.seed_kernel = (int (*)(const Dev *, int, void *))dlsym(u.dl, "va_user_seed_kernel");
-    u.predict = (int (*)(const PredictArgs *, int, void *))dlsym(u.dl, "va_user_predict");       // (optional: no flat struct, no predictor)
-    if (!info || !u.launch || !u.prepare) { dlclose(u.dl); return fail(VA_EINVAL, "%s lacks va_user_rhs_info / va_user_launch_eval / va_user_prepare_eval", path); }
-    int ri[5] = {0, 0, 0, 0, 0};           // (NP, D, NSTIM, sizeof(Dev), sizeof(SeedState))
-    info(ri);
-    const int dev_bytes = ri[3], seed_bytes = ri[4];
-    if (dev_bytes != (int)sizeof(Dev) || seed_bytes != (int)sizeof(SeedState)) {
+    typedef int (*table_fn)(RhsTable *, int);
+    table_fn table = (table_fn)dlsym(u.dl, "va_user_rhs_table");
+    if (!table) { dlclose(u.dl); return fail(VA_EINVAL, "%s lacks va_user_rhs_table", path); }
+    RhsTable &t = u.table;
+    const int table_bytes = table(&t, (int)sizeof(RhsTable));         // (fills t only when the sizes agree)
+    if (table_bytes != (int)sizeof(RhsTable) || t.dev_bytes != (int)sizeof(Dev) || t.seed_bytes != (int)sizeof(SeedState)
+        || t.predict_bytes != (int)sizeof(PredictArgs)) {
         dlclose(u.dl);
-        return fail(VA_EINVAL, "%s was built against different headers (Dev %d vs %zu bytes): rebuild it", path, dev_bytes, sizeof(Dev));
+        return fail(VA_EINVAL, "%s was built against different headers (table %d vs %zu bytes, Dev %d vs %zu bytes): rebuild it", path,
+                    table_bytes, sizeof(RhsTable), t.dev_bytes, sizeof(Dev));
     }
-    u.NP = ri[0]; u.D = ri[1]; u.NSTIM = ri[2];
     if (info_fn vinfo = (info_fn)dlsym(u.dl, "va_user_variant_info")) {
         int uv[UV_N];
         vinfo(uv);
         u.variant = ModuleVariant::decode(uv);
-        u.launch_var = (void (*)(const Dev *, void *))dlsym(u.dl, "va_user_launch_variant");
-        u.prepare_var = (int (*)(const Dev *))dlsym(u.dl, "va_user_prepare_variant");
-        if (!u.launch_var || !u.prepare_var) u.variant.kernel = 0;
+        if (!t.eval_var) u.variant.kernel = 0;
     }
     if (info_fn cmap = (info_fn)dlsym(u.dl, "va_user_colp_map")) {
         // (S <= RHS_MAX_NP and V <= CP_VMAX by construction: the generator checks both)
-        u.colp.assign(2 + RHS_MAX_NP + (size_t)CP_VMAX * (u.D > 0 ? u.D : 1), 0);
+        u.colp.assign(2 + RHS_MAX_NP + (size_t)CP_VMAX * (t.D > 0 ? t.D : 1), 0);
         cmap(u.colp.data());
-        u.colp.resize(2 + (size_t)u.colp[0] + (size_t)u.colp[1] * u.D);
+        u.colp.resize(2 + (size_t)u.colp[0] + (size_t)u.colp[1] * t.D);
     }
     if (u.colp.empty()) u.variant.n_colp_vectors = 0;
     // past RHS_BIG_NP parameters a module has no flat kernel: it must carry the column-parameter form (the kernels that
     // run it are checked problem by problem, va_problem_create)
-    if (u.NP < 0 || (u.NP > RHS_BIG_NP && u.colp.empty())) {
+    if (t.NP < 0 || (t.NP > RHS_BIG_NP && u.colp.empty())) {
         dlclose(u.dl);
-        return fail(VA_EUNSUPPORTED, "%s: NP=%d > %d and no column-parameter form", path, u.NP, RHS_BIG_NP);
+        return fail(VA_EUNSUPPORTED, "%s: NP=%d > %d and no column-parameter form", path, t.NP, RHS_BIG_NP);
     }
     g_user_rhs.push_back(u);
     *rhs_id = VA_RHS_USER_BASE + (int32_t)g_user_rhs.size() - 1;
@@ -1036,7 +1024,7 @@ int va_problem_create(const va_problem_desc *d, va_handle *out)
     TRY(alloc_problem_data(h.get(), d, plan, data));
     TRY(alloc_solver_state(h.get()));         // (reads dv.cpv / dv.cps: after plan_problem)
     TRY(upload_problem_data(h.get(), d, user, plan, data));
-    TRY(choose_persist(h.get(), d, user));
+    TRY(choose_persist(h.get(), d));
     TRY(finish_create(h.get()));
     *out = h.release();
     return VA_OK;
@@ -1061,7 +1049,7 @@ int va_nnet_problem_create(const va_nnet_desc *d, va_handle *out)
     if (int rc = plan_nnet(d, cu_count(d->device), plan, &why)) return fail(rc, "%s", why);
     HandleOwner h;
     TRY(begin_create(d->device, d->stream, d->lbfgs_m, d->max_beta, d->keep_paths, h));
-    h->rhs = -1; h->is_nnet = true; h->user_act = user_act;
+    h->rhs = -1; h->is_nnet = true; h->nn_act = user_act;
     fill_nnet_dims(h.get(), d, plan);
     TRY(create_nnet_image(h.get(), d, plan));
     TRY(finish_create(h.get()));
@@ -1189,7 +1177,7 @@ int va_predict(va_handle h, const double *x0, const double *p, int32_t T, double
     const int nstim = h->dv.pp.nstim;
     if (nstim > 0 && !stim) return fail(VA_EINVAL, "the model takes a stimulus of %d column(s): pass its %d rows from t0 on", nstim, n_steps + 1);
     if (nstim == 0 && stim) return fail(VA_EINVAL, "the model takes no stimulus, but one was passed");
-    if (h->user_rhs && !h->user_predict)
+    if (!h->rt.predict)
         return fail(VA_EUNSUPPORTED, "the model has no flat form f(x, i, p) for the integrator to call (more than %d parameters: "
                                      "its module carries the column-parameter form only)", RHS_BIG_NP);
     if ((int64_t)n_steps * substeps > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_steps x substeps does not fit 32-bit indexing");
@@ -1208,8 +1196,7 @@ int va_predict(va_handle h, const double *x0, const double *p, int32_t T, double
     if (np) HIPCHK(hipMemcpyAsync(p_d, p, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
     if (ns) HIPCHK(hipMemcpyAsync(st_d, stim, sizeof(double) * ns, hipMemcpyHostToDevice, h->stream));
     a.x0 = x0_d; a.p = p_d; a.stim = ns ? st_d : nullptr; a.out = out_d;
-    const hipError_t e = h->user_predict ? (hipError_t)h->user_predict(&a, (int)sizeof(PredictArgs), (void *)h->stream)
-                                         : launch_predict_builtin(a, h->stream);
+    const hipError_t e = h->rt.predict(a, h->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
         return fail(VA_EHIP, "k_predict launch: %s", hipGetErrorString(e));

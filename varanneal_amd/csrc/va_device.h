@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "va_core.h"
 #include "va_tile2.h"
 #include "va_tile3.h"
@@ -82,8 +84,56 @@ struct Dev {
     int cps, cpv, cpnsg;
 };
 
+// ------------------------------------------------------------------ one prepare-or-launch operation
+// Every evaluation kernel is reached through eval_op: a family names its instantiation ONCE and hands it here, so the
+// kernel that is opted in to its LDS (once per handle and device) cannot differ from the one that is launched.
+struct EvalOp { bool prepare; hipStream_t s; hipError_t err; };
+
+constexpr size_t LDS_DEFAULT_BYTES = 64 * 1024, LDS_OPTIN_BYTES = 160 * 1024;      // without / with the opt-in: a CU's whole LDS
+
+// (a multiple of 8: xcd_swizzle deals the workgroups over the 8 XCDs)
+inline int eval_grid(const Dims &dm) { return ((dm.B * dm.ntiles + 7) / 8) * 8; }
+
+template <class KERNEL>
+inline void eval_op(KERNEL kern, const Dev &dv, int threads, size_t lds, EvalOp &op)
+{
+    if (op.prepare) {
+        if (lds <= LDS_DEFAULT_BYTES) return;
+        const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_OPTIN_BYTES);
+        if (e != hipSuccess) op.err = e;
+        return;
+    }
+    hipLaunchKernelGGL(kern, dim3(eval_grid(dv.dm)), dim3(threads), lds, op.s, dv);
+}
+
+// the run-time discretisation as a compile-time constant: f(std::integral_constant<int, DISC_*>)
+template <class F>
+inline void with_disc(int disc, F &&f)
+{
+    switch (disc) {
+    case DISC_EULER: f(std::integral_constant<int, DISC_EULER>()); break;
+    case DISC_TRAPEZOID: f(std::integral_constant<int, DISC_TRAPEZOID>()); break;
+    case DISC_SH: f(std::integral_constant<int, DISC_SH>()); break;
+    default: f(std::integral_constant<int, DISC_FWDMAP>()); break;
+    }
+}
+
+// ------------------------------------------------------------------ one entry table per right-hand side
+// Everything the host launches that depends on the right-hand side.  The built-in Lorenz-96 fills one in va_kernels.hip
+// (builtin_rhs_table); a generated module fills one through its only entry point, va_user_rhs_table (va_user_rhs.hip).
+struct PredictArgs;
+struct RhsTable {
+    int bytes;                                 // sizeof(RhsTable), then the sizes of what crosses the boundary by value or by layout
+    int dev_bytes, seed_bytes, predict_bytes;
+    int NP, D, NSTIM;
+    void (*eval)(const Dev &, EvalOp &);       // the flat kernel (a module), the kernel dv.dm.emode names (built-in); a handle's copy: ITS kernel
+    void (*eval_var)(const Dev &, EvalOp &);   // a module's ONE carried column-run instantiation (va_user_variant_info describes it), or NULL
+    void (*seed)(const Dev &, EvalOp &);       // the persistent per-seed ladder kernel k_seed (va_persist.h), or NULL
+    hipError_t (*predict)(const PredictArgs &, hipStream_t);      // the RK4 predictor (va_predict.h), or NULL
+};
+void builtin_rhs_table(RhsTable &t);
+
 // launch wrappers (va_kernels.hip); all asynchronous on `s`
-void launch_eval(const Dev &dv, int rhs, hipStream_t s);
 void launch_ls(const Dev &dv, hipStream_t s);
 void launch_update(const Dev &dv, hipStream_t s);
 void launch_direction(const Dev &dv, hipStream_t s);
@@ -94,17 +144,11 @@ void launch_clamp_x(const Dev &dv, hipStream_t s);
 void launch_finalize_eval(const Dev &dv, hipStream_t s);
 size_t eval_lds_bytes(const Dev &dv);
 size_t update_lds_bytes(const Dims &dm);
-hipError_t prepare_eval(const Dev &dv, int rhs);   // once per handle: opt the kernel in to > 64 KiB of LDS on this device
-int eval_grid(const Dims &dm);
 // bounded problems: L-BFGS-B's direction step in k_direction's place (va_lbfgsb.hip)
 void launch_lbfgsb_dir(const Dev &dv, hipStream_t s);
 hipError_t prepare_lbfgsb(const Dev &dv);
-// the persistent per-seed ladder kernel for the built-in right-hand side (va_persist.h): launch == false opts the
-// instantiation in to its LDS on the current device, launch == true launches B * ntiles workgroups, one per CU
-hipError_t seed_kernel_builtin(const Dev &dv, bool launch, hipStream_t s);
-// streaming column strips (va_eval5.hip)
-void launch_eval5(const Dev &dv, hipStream_t s);
-hipError_t prepare_eval5(const Dev &dv);
+// streaming column strips for the built-in right-hand side (va_eval5.hip)
+void eval5_builtin(const Dev &dv, EvalOp &op);
 size_t eval5_lds(const Dev &dv);
 
 }  // namespace va

@@ -146,17 +146,11 @@ inline size_t eval3_lds_bytes(const Dims &dm)
     return sizeof(double) * (elems + (strips < 64 ? 64 : strips));
 }
 
-// launch one instantiation (the caller has checked that dv.dm's geometry matches it)
+// launch or prepare one instantiation (the caller has checked that dv.dm's geometry matches it)
 template <class RHS, int DISC, int K, int DC, int NTMAX>
-inline void launch_eval3_one(const Dev &dv, hipStream_t s)
+inline void eval3_op(const Dev &dv, EvalOp &op)
 {
-    hipLaunchKernelGGL((k_eval3<RHS, DISC, K, DC, NTMAX>), dim3(eval_flat_grid(dv.dm)), dim3(dv.dm.NT), eval3_lds_bytes(dv.dm), s, dv);
-}
-template <class RHS, int DISC, int K, int DC, int NTMAX>
-inline hipError_t prepare_eval3_one(const Dev &dv)
-{
-    if (eval3_lds_bytes(dv.dm) <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute((const void *)k_eval3<RHS, DISC, K, DC, NTMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    eval_op(k_eval3<RHS, DISC, K, DC, NTMAX>, dv, dv.dm.NT, eval3_lds_bytes(dv.dm), op);
 }
 
 }  // namespace va

@@ -373,17 +373,14 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
 
 inline size_t eval4_lds_bytes(const Dev &dv) { return sizeof(double) * (size_t)dv.g4.NW * dv.g4.WAVE; }
 
-// launch one instantiation (the caller has checked that dv.g4 / dv.dm.maxr / dv.dm.disc match it)
+// launch or prepare one instantiation (the caller has checked that dv.g4 / dv.dm.maxr / dv.dm.disc match it).
+// Sub-tiles per wave: 1.  (Measured at C3, SUB = 3 -- one wave per SIMD, 256 workgroups -- against SUB = 1 -- three waves
+// per SIMD: 8.7 vs 8.0 us.  A lone wave has nothing to hide its LDS and matrix-pipe latencies behind, so only SUB = 1 is
+// compiled; the kernel keeps the loop.)
 template <class RHS, int DISC, int K, int DC, int WS>
-inline void launch_eval4_one(const Dev &dv, hipStream_t s)
+inline void eval4_op(const Dev &dv, EvalOp &op)
 {
-    hipLaunchKernelGGL((k_eval4<RHS, DISC, K, DC, WS, 1>), dim3(eval_flat_grid(dv.dm)), dim3(256), eval4_lds_bytes(dv), s, dv);
-}
-template <class RHS, int DISC, int K, int DC, int WS>
-inline hipError_t prepare_eval4_one(const Dev &dv)
-{
-    if (eval4_lds_bytes(dv) <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute((const void *)k_eval4<RHS, DISC, K, DC, WS, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    eval_op(k_eval4<RHS, DISC, K, DC, WS, 1>, dv, 256, eval4_lds_bytes(dv), op);
 }
 
 }  // namespace va

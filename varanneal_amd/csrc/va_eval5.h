@@ -495,65 +495,33 @@ inline size_t eval5_lds_bytes(const Dev &dv)
     return sizeof(double) * (size_t)dv.g5.WPG * tile5_wave_doubles(dv.g5, dv.lsrun ? dv.g5.nslot_ls : dv.g5.nslot, dv.lsrun != 0, dv.g5.warr != 0);
 }
 
-// launch (or, once per handle and device, opt in to > 64 KiB of LDS) the instantiation the handle's geometry and
-// this launch's kind call for: ring depth and "line-search points possible" are template parameters
-// weight arrays / data every nskip-th row (Geo5::warr): a three-slot ring only
-template <class RHS, int DISC, int DC, bool XDPP>
-inline hipError_t eval5_slots_w(const Dev &dv, bool prepare, hipStream_t s)
+// The instantiation the handle's geometry and the launch kind dv.lsrun call for: ring depth, "line-search points possible",
+// the DPP exchange and the weight arrays are template parameters.  (Weight arrays / data every nskip-th row, Geo5::warr: a
+// three-slot ring only.)
+template <class RHS, int DISC, int DC, bool LSRUN, bool XDPP>
+inline void eval5_ring(const Dev &dv, EvalOp &op)
 {
-    const int threads = 64 * dv.g5.WPG;
-    if (prepare) {
-        hipError_t err = hipSuccess;
-        Dev t = dv;
-        for (int ls = 0; ls < 2; ++ls) {
-            t.lsrun = ls;
-            if (eval5_lds_bytes(t) <= 64 * 1024) continue;
-            hipError_t e = ls ? hipFuncSetAttribute((const void *)k_eval5<RHS, DISC, DC, 3, true, XDPP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-                              : hipFuncSetAttribute((const void *)k_eval5<RHS, DISC, DC, 3, false, XDPP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) err = e;
-        }
-        return err;
-    }
+    const int threads = 64 * dv.g5.WPG, ns = LSRUN ? dv.g5.nslot_ls : dv.g5.nslot;
     const size_t lds = eval5_lds_bytes(dv);
-    const int grid = ((dv.dm.B * dv.dm.ntiles + 7) / 8) * 8;
-    if (dv.lsrun) hipLaunchKernelGGL((k_eval5<RHS, DISC, DC, 3, true, XDPP, true>), dim3(grid), dim3(threads), lds, s, dv);
-    else hipLaunchKernelGGL((k_eval5<RHS, DISC, DC, 3, false, XDPP, true>), dim3(grid), dim3(threads), lds, s, dv);
-    return hipSuccess;
-}
-template <class RHS, int DISC, int DC, bool XDPP>
-inline hipError_t eval5_slots(const Dev &dv, bool prepare, hipStream_t s)
-{
-    if (dv.g5.warr) return eval5_slots_w<RHS, DISC, DC, XDPP>(dv, prepare, s);
-    const int threads = 64 * dv.g5.WPG;
-    if (prepare) {
-        hipError_t err = hipSuccess;
-        Dev t = dv;
-        for (int ls = 0; ls < 2; ++ls) {          // both launch kinds of the handle
-            t.lsrun = ls;
-            if (eval5_lds_bytes(t) <= 64 * 1024) continue;
-            const int ns = ls ? t.g5.nslot_ls : t.g5.nslot;
-            hipError_t e = hipSuccess;
-#define VA_E5_ATTR(NSL, LS) e = hipFuncSetAttribute((const void *)k_eval5<RHS, DISC, DC, NSL, LS, XDPP, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-            if (ls) { if (ns == 3) VA_E5_ATTR(3, true); else VA_E5_ATTR(4, true); }
-            else { if (ns == 3) VA_E5_ATTR(3, false); else VA_E5_ATTR(4, false); }
-#undef VA_E5_ATTR
-            if (e != hipSuccess) err = e;
-        }
-        return err;
-    }
-    const size_t lds = eval5_lds_bytes(dv);
-    const int ns = dv.lsrun ? dv.g5.nslot_ls : dv.g5.nslot;
-    const int grid = ((dv.dm.B * dv.dm.ntiles + 7) / 8) * 8;
-#define VA_E5_GO(NSL, LS) hipLaunchKernelGGL((k_eval5<RHS, DISC, DC, NSL, LS, XDPP, false>), dim3(grid), dim3(threads), lds, s, dv)
-    if (dv.lsrun) { if (ns == 3) VA_E5_GO(3, true); else VA_E5_GO(4, true); }
-    else { if (ns == 3) VA_E5_GO(3, false); else VA_E5_GO(4, false); }
-#undef VA_E5_GO
-    return hipSuccess;
+    if (dv.g5.warr) eval_op(k_eval5<RHS, DISC, DC, 3, LSRUN, XDPP, true>, dv, threads, lds, op);
+    else if (ns == 3) eval_op(k_eval5<RHS, DISC, DC, 3, LSRUN, XDPP, false>, dv, threads, lds, op);
+    else eval_op(k_eval5<RHS, DISC, DC, 4, LSRUN, XDPP, false>, dv, threads, lds, op);
 }
 template <class RHS, int DISC, int DC>
-inline hipError_t eval5_run(const Dev &dv, bool prepare, hipStream_t s)
+inline void eval5_kind(const Dev &dv, EvalOp &op)
 {
-    return dv.g5.xdpp ? eval5_slots<RHS, DISC, DC, t5_dpp_ok<RHS>()>(dv, prepare, s) : eval5_slots<RHS, DISC, DC, false>(dv, prepare, s);
+    constexpr bool X = t5_dpp_ok<RHS>();
+    if (dv.lsrun) { if (dv.g5.xdpp) eval5_ring<RHS, DISC, DC, true, X>(dv, op); else eval5_ring<RHS, DISC, DC, true, false>(dv, op); }
+    else { if (dv.g5.xdpp) eval5_ring<RHS, DISC, DC, false, X>(dv, op); else eval5_ring<RHS, DISC, DC, false, false>(dv, op); }
+}
+// launch the kind dv.lsrun names; prepare BOTH launch kinds of the handle (their LDS sizes differ): the same selection,
+// run twice on a copy of Dev
+template <class RHS, int DISC, int DC>
+inline void eval5_op(const Dev &dv, EvalOp &op)
+{
+    if (!op.prepare) { eval5_kind<RHS, DISC, DC>(dv, op); return; }
+    Dev t = dv;
+    for (t.lsrun = 0; t.lsrun < 2; ++t.lsrun) eval5_kind<RHS, DISC, DC>(t, op);
 }
 
 }  // namespace va

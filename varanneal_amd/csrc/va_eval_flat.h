@@ -224,7 +224,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_eval(const Dev dv)
         eval_epilogue<true>(dv, b, lane, reinterpret_cast<SeedHot *>(red), dv.epi);
 }
 
-// LDS bytes / grid of the flat-mapped kernel
+// LDS bytes of the flat-mapped kernel
 inline size_t eval_flat_lds_bytes(const Dims &dm)
 {
     const int HL = dm.disc == DISC_SH ? 2 : 1;
@@ -232,36 +232,13 @@ inline size_t eval_flat_lds_bytes(const Dims &dm)
     return sizeof(double) * ((size_t)3 * (dm.T + HL + 1) * dm.D + (dm.lin ? (size_t)dm.T * dm.D : 0) + (EVAL_THREADS / 64) * KR
                              + (dm.tdp ? (size_t)(dm.T + HL + 1) * dm.NPt : 0));
 }
-inline int eval_flat_grid(const Dims &dm) { return ((dm.B * dm.ntiles + 7) / 8) * 8; }
 
-// wide states: opt the kernel in to the CU's full LDS on the CURRENT device (the attribute is per
-// device; called once per problem handle, va_problem_create)
+// launch the flat kernel, or opt it in to the CU's full LDS on the CURRENT device (wide states; the attribute is per
+// device: once per problem handle, va_problem_create)
 template <class RHS>
-inline hipError_t prepare_eval_rhs(const Dev &dv)
+inline void eval_flat_op(const Dev &dv, EvalOp &op)
 {
-    if (eval_flat_lds_bytes(dv.dm) <= 64 * 1024) return hipSuccess;
-    const void *k = nullptr;
-    switch (dv.dm.disc) {
-    case DISC_EULER: k = (const void *)k_eval<RHS, DISC_EULER>; break;
-    case DISC_TRAPEZOID: k = (const void *)k_eval<RHS, DISC_TRAPEZOID>; break;
-    case DISC_SH: k = (const void *)k_eval<RHS, DISC_SH>; break;
-    default: k = (const void *)k_eval<RHS, DISC_FWDMAP>; break;
-    }
-    return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    with_disc(dv.dm.disc, [&](auto disc) { eval_op(k_eval<RHS, decltype(disc)::value>, dv, EVAL_THREADS, eval_flat_lds_bytes(dv.dm), op); });
 }
-
-template <class RHS>
-inline void launch_eval_rhs(const Dev &dv, hipStream_t s)
-{
-    const dim3 grid(eval_flat_grid(dv.dm)), block(EVAL_THREADS);
-    const size_t lds = eval_flat_lds_bytes(dv.dm);
-    switch (dv.dm.disc) {
-    case DISC_EULER: hipLaunchKernelGGL((k_eval<RHS, DISC_EULER>), grid, block, lds, s, dv); break;
-    case DISC_TRAPEZOID: hipLaunchKernelGGL((k_eval<RHS, DISC_TRAPEZOID>), grid, block, lds, s, dv); break;
-    case DISC_SH: hipLaunchKernelGGL((k_eval<RHS, DISC_SH>), grid, block, lds, s, dv); break;
-    default: hipLaunchKernelGGL((k_eval<RHS, DISC_FWDMAP>), grid, block, lds, s, dv); break;
-    }
-}
-
 
 }  // namespace va

@@ -31,42 +31,18 @@ namespace va {
 
 size_t eval_lds_bytes(const Dev &dv)
 {
-    const Dims &dm = dv.dm;
-    if (dm.emode == 4) return sizeof(double) * (size_t)dv.g4.NW * dv.g4.WAVE;
-    if (dm.emode == 5) return eval5_lds(dv);
-    if (dm.emode == 1) return eval_flat_lds_bytes(dm);
-    const int HL = dm.disc == DISC_SH ? 2 : 1;
-    const size_t elems = (size_t)tile3_stage_elems(dm.maxr, dm.D, dm.ghost, dm.RY, HL + 1) + tile3_s_elems(dm.maxr, dm.D, dm.ghost, dm.RY);
-    const size_t strips = (size_t)(dm.NT / 64) * 5 * t3_strip_stride(dm.NP);      // (>= 512 B: the tail stages the seed's state there)
-    return sizeof(double) * (elems + (strips < 64 ? 64 : strips));
-}
-
-int eval_grid(const Dims &dm) { return ((dm.B * dm.ntiles + 7) / 8) * 8; }
-
-// launch, or (prepare) opt the instantiation in to the LDS it needs on the current device
-struct EvalOp { bool prepare; hipStream_t s; hipError_t err; };
-
-template <class KERNEL>
-static void eval_op(KERNEL kern, const Dev &dv, int threads, EvalOp &op)
-{
-    const size_t lds = eval_lds_bytes(dv);
-    if (op.prepare) {
-        if (lds > 64 * 1024)
-            op.err = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return;
+    switch (dv.dm.emode) {
+    case 5: return eval5_lds(dv);
+    case 4: return eval4_lds_bytes(dv);
+    case 3: return eval3_lds_bytes(dv.dm);
+    default: return eval_flat_lds_bytes(dv.dm);
     }
-    hipLaunchKernelGGL(kern, dim3(eval_grid(dv.dm)), dim3(threads), lds, op.s, dv);
 }
 
 template <class RHS, int K, int DC, int NTMAX>
 static void eval3_rhs(const Dev &dv, EvalOp &op)
 {
-    switch (dv.dm.disc) {
-    case DISC_EULER: eval_op(k_eval3<RHS, DISC_EULER, K, DC, NTMAX>, dv, dv.dm.NT, op); break;
-    case DISC_TRAPEZOID: eval_op(k_eval3<RHS, DISC_TRAPEZOID, K, DC, NTMAX>, dv, dv.dm.NT, op); break;
-    case DISC_SH: eval_op(k_eval3<RHS, DISC_SH, K, DC, NTMAX>, dv, dv.dm.NT, op); break;
-    default: eval_op(k_eval3<RHS, DISC_FWDMAP, K, DC, NTMAX>, dv, dv.dm.NT, op); break;
-    }
+    with_disc(dv.dm.disc, [&](auto disc) { eval3_op<RHS, decltype(disc)::value, K, DC, NTMAX>(dv, op); });
 }
 
 // D fixed at compile time for the state size of BASELINE config 4 (D = 200, 256-thread groups); any
@@ -82,26 +58,10 @@ static void eval3_d(const Dev &dv, EvalOp &op)
     else eval3_rhs<RHS, K, 0, 1024>(dv, op);
 }
 
-template <class RHS, int K, int DC, int WS, int SUB>
-static void eval4_disc(const Dev &dv, EvalOp &op)
-{
-    switch (dv.dm.disc) {
-    case DISC_EULER: eval_op(k_eval4<RHS, DISC_EULER, K, DC, WS, SUB>, dv, 256, op); break;
-    case DISC_TRAPEZOID: eval_op(k_eval4<RHS, DISC_TRAPEZOID, K, DC, WS, SUB>, dv, 256, op); break;
-    case DISC_SH: eval_op(k_eval4<RHS, DISC_SH, K, DC, WS, SUB>, dv, 256, op); break;
-    default: eval_op(k_eval4<RHS, DISC_FWDMAP, K, DC, WS, SUB>, dv, 256, op); break;
-    }
-}
-
-// sub-tiles per wave: 1, or 2 / 3 for grids of a few wave-tiles per SIMD (compiled for the
-// scalar-weight variant with D fixed only: that is where such grids are the BASELINE configs)
 template <class RHS, int K, int DC, int WS>
 static void eval4_rhs(const Dev &dv, EvalOp &op)
 {
-    // (measured at C3, SUB = 3 -- one wave per SIMD, 256 workgroups -- against SUB = 1 -- three waves
-    // per SIMD: 8.7 vs 8.0 us.  A lone wave has nothing to hide its LDS and matrix-pipe latencies
-    // behind, so only SUB = 1 is compiled; the kernel keeps the loop.)
-    eval4_disc<RHS, K, DC, WS, 1>(dv, op);
+    with_disc(dv.dm.disc, [&](auto disc) { eval4_op<RHS, decltype(disc)::value, K, DC, WS>(dv, op); });
 }
 
 // D = 20 (examples/Lorenz96_D20, BASELINE configs 1-3) is compiled with D as a constant; scalar RM /
@@ -117,13 +77,11 @@ static void eval4_d(const Dev &dv, EvalOp &op)
     } else { if (ws) eval4_rhs<RHS, K, 0, 1>(dv, op); else eval4_rhs<RHS, K, 0, 0>(dv, op); }
 }
 
-static void eval_dispatch(const Dev &dv, int rhs, EvalOp &op)
+// the built-in right-hand side's evaluation kernel: the one dv.dm.emode names
+static void eval_builtin(const Dev &dv, EvalOp &op)
 {
-    (void)rhs;                 // VA_RHS_LORENZ96 is the only built-in RHS
-    if (dv.dm.emode == 5) {
-        if (op.prepare) op.err = prepare_eval5(dv);
-        else launch_eval5(dv, op.s);
-    } else if (dv.dm.emode == 4) {
+    if (dv.dm.emode == 5) eval5_builtin(dv, op);
+    else if (dv.dm.emode == 4) {
         switch (dv.dm.maxr) {
         case 4: eval4_d<RhsL96s, 4>(dv, op); break;
         case 5: eval4_d<RhsL96s, 5>(dv, op); break;
@@ -142,29 +100,16 @@ static void eval_dispatch(const Dev &dv, int rhs, EvalOp &op)
         case 7: eval3_d<RhsL96g, 7>(dv, op); break;
         default: eval3_d<RhsL96g, 8>(dv, op); break;
         }
-    } else {
-        if (op.prepare) op.err = prepare_eval_rhs<RhsL96>(dv);
-        else launch_eval_rhs<RhsL96>(dv, op.s);
-    }
+    } else eval_flat_op<RhsL96>(dv, op);
 }
 
-void launch_eval(const Dev &dv, int rhs, hipStream_t s)
+// Lorenz-96 (VA_RHS_LORENZ96, the only built-in right-hand side).  The RK4 predictor (va_predict.h): one wave per workgroup
+// for D <= 64, 1 .. 4 columns per lane beyond
+void builtin_rhs_table(RhsTable &t)
 {
-    EvalOp op{false, s, hipSuccess};
-    eval_dispatch(dv, rhs, op);
+    t = RhsTable{(int)sizeof(RhsTable), (int)sizeof(Dev), (int)sizeof(SeedState), (int)sizeof(PredictArgs), RhsL96::NP, 0, 0,
+                 eval_builtin, nullptr, seed_op<RhsL96>, launch_predict<RhsL96, 0>};
 }
-
-hipError_t prepare_eval(const Dev &dv, int rhs)
-{
-    EvalOp op{true, nullptr, hipSuccess};
-    eval_dispatch(dv, rhs, op);
-    return op.err;
-}
-
-hipError_t seed_kernel_builtin(const Dev &dv, bool launch, hipStream_t s) { return seed_kernel_op<RhsL96>(dv, launch, s); }
-
-// the RK4 predictor (va_predict.h) for the built-in right-hand side: one wave per workgroup for D <= 64, 1 .. 4 columns per lane beyond
-hipError_t launch_predict_builtin(const PredictArgs &a, hipStream_t s) { return launch_predict<RhsL96, 0>(a, s); }
 
 // ------------------------------------------------------------------ K2: tails as kernels of their own
 // (the network action, whose evaluation is several kernels, and grids too large to fold the tail

@@ -582,35 +582,29 @@ __global__ __launch_bounds__(PZ_THREADS) void k_seed(const Dev dv)
     PZ_MARK_FLUSH(dv.pz.stamps, cyc);
 }
 
-inline const void *seed_kernel_of(const void *const k[4], int disc)
-{
-    return k[disc == DISC_EULER ? 0 : disc == DISC_TRAPEZOID ? 1 : disc == DISC_SH ? 2 : 3];
-}
-
-// launch == false: opt the instantiation in to the LDS it needs on the current device (once per handle);
-// launch == true: dv.dm.B * dv.dm.ntiles workgroups, one per CU (each takes more than half of a CU's LDS, and the host
+// prepare: opt the instantiation in to the LDS it needs on the current device (once per handle); launch:
+// dv.dm.B * dv.dm.ntiles workgroups, one per CU (each takes more than half of a CU's LDS, and the host
 // never asks for more workgroups than the device has CUs).  A PLAIN launch: it has the residency of a cooperative one
 // (MI355X_MICROARCH.md, "Residency and cooperative launch"), costs 15-19 us less on the host, and -- measured in round 4 --
 // a process that made a cooperative launch under rocprofv3 --kernel-trace dies in the tool's exit handler.  Should the
 // workgroups not all be resident after all (another process holding CUs), the bounded polls end the launch with
 // abort_flag = 1 and the host falls back to the three-launch cycle.
-// A model of more than RHS_MAX_NP parameters (every generated module instantiates this) has no k_seed: refused, never launched.
+// Not through eval_op: the grid is the workgroups themselves (no rounding to the XCDs), every instantiation is opted in, and
+// the host falls back on a refused launch, so the launch call is the one that returns its error (op.err).
+// A right-hand side without k_seed (more than RHS_MAX_NP parameters, or no flat struct) has no seed_op: its table says NULL.
+template <class RHS> constexpr bool seed_kernel_exists() { return EP_GP + RHS::NP <= EP_N && rhs_flat<RHS>::value; }
+
 template <class RHS>
-inline hipError_t seed_kernel_op(const Dev &dv, bool launch, hipStream_t s)
+inline void seed_op(const Dev &dv, EvalOp &op)
 {
-    if constexpr (EP_GP + RHS::NP > EP_N || !rhs_flat<RHS>::value) {
-        (void)dv; (void)launch; (void)s;
-        return hipErrorNotSupported;
-    } else {
-        const void *const ks[4] = {(const void *)k_seed<RHS, DISC_EULER>, (const void *)k_seed<RHS, DISC_TRAPEZOID>,
-                                   (const void *)k_seed<RHS, DISC_SH>, (const void *)k_seed<RHS, DISC_FWDMAP>};
-        const void *k = seed_kernel_of(ks, dv.dm.disc);
+    with_disc(dv.dm.disc, [&](auto disc) {
+        const void *k = (const void *)k_seed<RHS, decltype(disc)::value>;
         const int HL = dv.dm.disc == DISC_SH ? 2 : 1;
         const size_t lds = 8 * persist_lds_doubles(dv.dm.T, dv.dm.D, dv.dm.L, RHS::NP, dv.dm.NPest, dv.dm.m, HL, dv.dm.ntiles);
-        if (!launch) return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         void *args[1] = {(void *)&dv};
-        return hipLaunchKernel(k, dim3(dv.dm.B * dv.dm.ntiles), dim3(PZ_THREADS), args, lds, s);
-    }
+        op.err = op.prepare ? hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_OPTIN_BYTES)
+                            : hipLaunchKernel(k, dim3(dv.dm.B * dv.dm.ntiles), dim3(PZ_THREADS), args, lds, op.s);
+    });
 }
 
 }  // namespace va

@@ -284,8 +284,5 @@ inline hipError_t launch_predict(const PredictArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-// the built-in right-hand side's instantiations (va_kernels.hip)
-hipError_t launch_predict_builtin(const PredictArgs &a, hipStream_t s);
-
 }  // namespace va
 #endif

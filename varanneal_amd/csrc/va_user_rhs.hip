@@ -2,8 +2,11 @@
 //
 // varanneal_amd/codegen.py traces the user's `f(t, x, p)` (the callable of set_model,
 // varanneal/va_ode.py:56-67), differentiates it symbolically and writes a header that
-// defines `struct RhsUser` with f, J^T v and (df/dp)^T v.  This file instantiates the
-// flat-mapped tile kernel for it; it is compiled with
+// defines `struct RhsUser` with f, J^T v and (df/dp)^T v.  This file instantiates the model's
+// kernels -- the flat-mapped tile kernel, the persistent ladder kernel, the RK4 predictor and at most
+// ONE column-run kernel -- and exports ONE entry point, va_user_rhs_table, which fills the table of
+// launchers (RhsTable, va_device.h) the host reaches them through; two more functions return data
+// (va_user_variant_info, va_user_colp_map).  It is compiled with
 //     hipcc --offload-arch=gfx950 -shared -DVA_USER_RHS_HEADER='"<header>"' va_user_rhs.hip
 // and registered through va_rhs_load_module().  The reference replays an ADOL-C tape of f
 // instead (_autodiffmin.py:32-58).
@@ -20,56 +23,6 @@
 #include VA_USER_RHS_HEADER
 
 namespace {
-// A model of more than RHS_BIG_NP parameters has no flat struct (RhsUser::FLAT = false): nothing of the flat kernel or of
-// k_seed is instantiated, and the host never asks for them (va_problem_create refuses such problems on any other kernel)
-template <class R> void user_launch_eval(const va::Dev &dv, hipStream_t s)
-{
-    if constexpr (va::rhs_flat<R>::value) va::launch_eval_rhs<R>(dv, s);
-    else { (void)dv; (void)s; }
-}
-template <class R> hipError_t user_prepare_eval(const va::Dev &dv)
-{
-    if constexpr (va::rhs_flat<R>::value) return va::prepare_eval_rhs<R>(dv);
-    else { (void)dv; return hipErrorNotSupported; }
-}
-}  // namespace
-
-extern "C" {
-
-// (NP, D, NSTIM, sizeof(Dev), sizeof(SeedState)) -- checked by va_rhs_load_module
-void va_user_rhs_info(int *out)
-{
-    out[0] = va::RhsUser::NP; out[1] = va::RhsUser::D; out[2] = va::RhsUser::NSTIM;
-    out[3] = (int)sizeof(va::Dev); out[4] = (int)sizeof(va::SeedState);
-}
-
-void va_user_launch_eval(const va::Dev *dv, void *stream)
-{
-    user_launch_eval<va::RhsUser>(*dv, (hipStream_t)stream);
-}
-
-// once per problem handle, on the handle's device: opt the kernel in to the LDS it needs
-int va_user_prepare_eval(const va::Dev *dv)
-{
-    return (int)user_prepare_eval<va::RhsUser>(*dv);
-}
-
-// the persistent per-seed ladder kernel (va_persist.h) for this model: few seeds, short paths
-int va_user_seed_kernel(const va::Dev *dv, int launch, void *stream)
-{
-    return (int)va::seed_kernel_op<va::RhsUser>(*dv, launch != 0, (hipStream_t)stream);
-}
-
-// the RK4 predictor (va_predict.h) for this model: only a module with a flat struct (the generator says so: VA_USER_FLAT)
-// has the f(x_row, i, ...) the integrator calls.  args_bytes: sizeof(PredictArgs) as the caller knows it
-#ifdef VA_USER_FLAT
-int va_user_predict(const va::PredictArgs *a, int args_bytes, void *stream)
-{
-    if (args_bytes != (int)sizeof(va::PredictArgs)) return (int)hipErrorInvalidValue;
-    return (int)va::launch_predict<va::RhsUser, va::RhsUser::D>(*a, (hipStream_t)stream);
-}
-#endif
-
 // Besides the flat kernel a module may carry ONE instantiation of a column-run kernel, named when the module
 // was generated (va_eval_plan; -DVA_USER_EK=3|4 -DVA_USER_DISC -DVA_USER_K -DVA_USER_W):
 //   EK = 4: the model's column form (struct RhsUserCol: a translation-invariant stencil, or a small dense
@@ -78,7 +31,6 @@ int va_user_predict(const va::PredictArgs *a, int args_bytes, void *stream)
 //   EK = 3: a stencil's ghosted form (struct RhsUserG) on the workgroup kernel k_eval3; W = threads per workgroup
 // A model in column-parameter form (struct RhsUserColP: a stencil with per-column parameter vectors) takes the place of
 // the column form for EK = 4 and 5.
-// (the integers are named in va_core.h: UV_*)
 #if defined(VA_USER_COLP)
 #define VA_USER_COLT va::RhsUserColP
 #elif defined(VA_USER_COL)
@@ -91,6 +43,41 @@ int va_user_predict(const va::PredictArgs *a, int args_bytes, void *stream)
 #elif defined(VA_USER_EK) && VA_USER_EK == 3 && defined(VA_USER_GHOST)
 #define VA_USER_VARIANT 3
 #endif
+// the carried instantiation, named once
+#if !defined(VA_USER_VARIANT)
+constexpr void (*user_eval_var)(const va::Dev &, va::EvalOp &) = nullptr;
+#elif VA_USER_VARIANT == 5
+constexpr auto user_eval_var = va::eval5_op<VA_USER_COLT, VA_USER_DISC, VA_USER_COLT::D>;
+#elif VA_USER_VARIANT == 4
+constexpr auto user_eval_var = va::eval4_op<VA_USER_COLT, VA_USER_DISC, VA_USER_K, VA_USER_COLT::D, VA_USER_W != 0>;
+#else
+constexpr auto user_eval_var = va::eval3_op<va::RhsUserG, VA_USER_DISC, VA_USER_K, va::RhsUserG::D, VA_USER_W>;     // (D compiled in, as the built-in's D = 200)
+#endif
+
+// A model of more than RHS_BIG_NP parameters has no flat struct (RhsUser::FLAT = false): nothing of the flat kernel, of
+// k_seed or of the predictor is instantiated, and the host never asks for them (va_problem_create refuses such problems on
+// any other kernel than the carried one, va_predict refuses the handle).  (A template: only there are the branches not
+// taken left uninstantiated.)
+template <class R> void fill_table(va::RhsTable &t)
+{
+    t = va::RhsTable{(int)sizeof(va::RhsTable), (int)sizeof(va::Dev), (int)sizeof(va::SeedState), (int)sizeof(va::PredictArgs),
+                     R::NP, R::D, R::NSTIM, nullptr, user_eval_var, nullptr, nullptr};
+    if constexpr (va::rhs_flat<R>::value) { t.eval = va::eval_flat_op<R>; t.predict = va::launch_predict<R, R::D>; }
+    if constexpr (va::seed_kernel_exists<R>()) t.seed = va::seed_op<R>;
+}
+}  // namespace
+
+extern "C" {
+
+// The module's one entry point.  bytes: sizeof(RhsTable) as the caller knows it; returns the module's own, and fills *out
+// only when the two agree (va_rhs_load_module checks that, and the sizes of Dev, SeedState and PredictArgs in the table).
+int va_user_rhs_table(va::RhsTable *out, int bytes)
+{
+    if (bytes == (int)sizeof(va::RhsTable)) fill_table<va::RhsUser>(*out);
+    return (int)sizeof(va::RhsTable);
+}
+
+// (the integers are named in va_core.h: UV_*)
 void va_user_variant_info(int *out)
 {
     for (int k = 0; k < va::UV_N; ++k) out[k] = 0;
@@ -110,35 +97,6 @@ void va_user_variant_info(int *out)
 #endif
 #endif
 }
-#if defined(VA_USER_VARIANT) && VA_USER_VARIANT == 5
-void va_user_launch_variant(const va::Dev *dv, void *stream)
-{
-    (void)va::eval5_run<VA_USER_COLT, VA_USER_DISC, VA_USER_COLT::D>(*dv, false, (hipStream_t)stream);
-}
-int va_user_prepare_variant(const va::Dev *dv)
-{
-    return (int)va::eval5_run<VA_USER_COLT, VA_USER_DISC, VA_USER_COLT::D>(*dv, true, nullptr);
-}
-#elif defined(VA_USER_VARIANT) && VA_USER_VARIANT == 4
-void va_user_launch_variant(const va::Dev *dv, void *stream)
-{
-    va::launch_eval4_one<VA_USER_COLT, VA_USER_DISC, VA_USER_K, VA_USER_COLT::D, VA_USER_W != 0>(*dv, (hipStream_t)stream);
-}
-int va_user_prepare_variant(const va::Dev *dv)
-{
-    return (int)va::prepare_eval4_one<VA_USER_COLT, VA_USER_DISC, VA_USER_K, VA_USER_COLT::D, VA_USER_W != 0>(*dv);
-}
-#elif defined(VA_USER_VARIANT)
-void va_user_launch_variant(const va::Dev *dv, void *stream)
-{
-    va::launch_eval3_one<va::RhsUserG, VA_USER_DISC, VA_USER_K, va::RhsUserG::D, VA_USER_W>(*dv, (hipStream_t)stream);     // (D compiled in, as the built-in's D = 200)
-}
-int va_user_prepare_variant(const va::Dev *dv)
-{
-    return (int)va::prepare_eval3_one<va::RhsUserG, VA_USER_DISC, VA_USER_K, va::RhsUserG::D, VA_USER_W>(*dv);
-}
-#endif
-
 #if defined(VA_USER_COLP)
 // the column-parameter form's map: (shared scalars S, vectors V), then the global parameter index of each shared scalar
 // and of each vector entry (v, column i) at S + v D + i
