@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--out", default=".")
     ap.add_argument("--predict", type=int, default=0, metavar="N",
                     help="hold the last N observations back and report the forecast error per rung")
+    ap.add_argument("--errorbars", action="store_true",
+                    help="print the final k +- sigma per seed (Laplace approximation: Annealer.param_covariance)")
     args = ap.parse_args()
 
     D = 20
@@ -90,6 +92,18 @@ def main():
         print("\nforecast of %d steps from every rung's estimate: RMS error on the measured components" % args.predict)
         for k, beta in enumerate(beta_array):
             print("beta = %3d   %s" % (beta, np.array2string(np.atleast_1d(err[..., k]), precision=4)))
+
+    if args.errorbars:
+        # inverse Hessian of the action as the package normalises it, at the last rung's minimisers; at large RF the
+        # exact Hessian can be indefinite along the flat direction, the Gauss-Newton part never is
+        try:
+            cov = anneal1.param_covariance()
+        except np.linalg.LinAlgError as e:
+            print("\n(%s)" % e)
+            cov = anneal1.param_covariance(gauss_newton=True)
+        cov = cov.reshape(-1, 1, 1)
+        for b, kk in enumerate(np.ravel(np.asarray(anneal1.minpaths)[..., -1, N_model * D])):
+            print("seed %d   k = %.4f +- %.2e" % (b, kk, np.sqrt(cov[b, 0, 0])))
 
     anneal1.save_paths(os.path.join(args.out, "paths.npy"))
     anneal1.save_params(os.path.join(args.out, "params.npy"))

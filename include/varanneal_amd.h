@@ -214,6 +214,23 @@ int va_get_minpath(va_handle h, int32_t seed, int32_t beta_idx, double *out);
 int va_predict(va_handle h, const double *x0, const double *p, int32_t T, double t0,
                int32_t n_steps, int32_t substeps, int32_t every, const double *stim, double *out);
 
+/* Hessian-vector products of the action: HV = (d^2 A / d[X | p_est]^2) V at npts points along nvec directions each, on the
+ * device (csrc/va_hvp.h: the gradient's linear phases run on tangent inputs, plus the model's second-derivative term).  The
+ * reference exposes adolc.hessian of a taped action; a handful of products recovers the block-banded Hessian with its
+ * parameter border (va_ode.Annealer.action_hessian), whose inverse is the Laplace approximation's covariance.
+ *   XP [npts*ld], V and HV [npts*nvec*ld], HOST, in the usual [X | p_est] packing (the directions of point i follow each
+ *        other); P [npts*NP] HOST, full parameter vectors whose estimated entries are taken from XP
+ *   rf_scale as in va_action_grad; gauss_newton != 0: the Gauss-Newton part 2 J^T W J only (no second derivatives of the model)
+ *   tile_rows 0, or the time rows a workgroup owns (the parameter rows are sums over tiles in tile order: the same bits for
+ *        the same geometry)
+ * The data, weights, discretisation, device and stream are the handle's.  The handle's BOUNDS are ignored: this is the
+ * Hessian of the unconstrained action.  Resident paths, seed states and captured graphs are left alone.
+ * VA_EINVAL: npts or nvec < 1, ld < n_var, tile_rows that do not fit the LDS.
+ * VA_EUNSUPPORTED (reason in va_last_error): network handles, p_time_dependent, rm_kind / rf_kind 2, modules with a split
+ * linear part, generated models without a flat form (more than 128 parameters), states too wide for one owned row. */
+int va_hess_vec(va_handle h, const double *XP, const double *P, const double *V, int32_t npts, int32_t nvec, int64_t ld,
+                double rf_scale, int32_t gauss_newton, int32_t tile_rows, double *HV);
+
 /* Measurement hook for bench.py: `iters` complete S1 evaluations (the same launch va_action_grad
  * makes: A, me, fe and the full gradient are formed every time) on the resident paths (those of
  * the last va_action_grad / va_anneal call), bracketed by HIP events on the handle's stream;

@@ -205,6 +205,8 @@ def lib():
                             C.POINTER(LbfgsOpts), c_dp, c_dp, c_ip, c_ip, c_lp, c_dp]
     L.va_get_minpath.argtypes = [h, C.c_int32, C.c_int32, c_dp]
     L.va_predict.argtypes = [h, c_dp, c_dp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp]
+    L.va_hess_vec.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, c_dp]
+    L.va_hess_vec.restype = C.c_int
     L.va_eval_timed.argtypes = [h, C.c_double, C.c_int32, C.POINTER(C.c_float)]
     L.va_eval_timed_prepare.argtypes = [h, C.c_double, C.c_int32]
     L.va_get_counters.argtypes = [h, c_lp, c_lp, c_lp]
@@ -235,7 +237,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_hess_vec", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -465,6 +467,33 @@ class Problem(object):
         check(self._L.va_predict(self._h, x0.ctypes.data_as(c_dp), p.ctypes.data_as(c_dp), T, float(t0), n_steps, substeps,
                                  every, st.ctypes.data_as(c_dp) if st is not None else None, out.ctypes.data_as(c_dp)))
         return out
+
+    def hess_vec(self, XP, V, rf_scale, P=None, gauss_newton=False, tile_rows=0):
+        """Hessian-vector products of the action on the device (va_hess_vec): XP (npts, n_var) points, V (npts, nvec, n_var)
+        directions (or (nvec, n_var) for one point), both packed [X | p_est].  P: (npts, NP) or (NP,) full parameter vectors
+        (estimated entries come from XP); default the handle's first seed's.  gauss_newton: 2 J^T W J only.  tile_rows: time
+        rows per workgroup (0: the library's choice).  Returns (npts, nvec, n_var).  The handle's bounds are ignored, its
+        resident state is left alone."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("hess_vec: the network action has no second derivatives here (ODE handles only)")
+        n = self.n_var
+        XP = _f64(XP).reshape(-1, n)
+        npts = XP.shape[0]
+        V = _f64(V)
+        one = V.ndim == 2 and npts == 1
+        V = V.reshape(npts, -1, n)
+        NP = self.desc.NP
+        if P is None:
+            P = np.ctypeslib.as_array(self.desc.P, shape=(NP,)) if (NP and not self.desc.p_time_dependent) else np.zeros(NP)
+        P = _f64(P).reshape(-1, NP) if NP else np.zeros((npts, 0))
+        if P.shape[0] == 1 and npts > 1:
+            P = np.ascontiguousarray(np.broadcast_to(P, (npts, NP)))
+        if P.shape[0] != npts:
+            raise ValueError("hess_vec: %d points but %d parameter vectors" % (npts, P.shape[0]))
+        HV = np.empty_like(V)
+        check(self._L.va_hess_vec(self._h, XP.ctypes.data_as(c_dp), P.ctypes.data_as(c_dp), V.ctypes.data_as(c_dp), npts,
+                                  V.shape[1], n, float(rf_scale), 1 if gauss_newton else 0, int(tile_rows), HV.ctypes.data_as(c_dp)))
+        return HV[0] if one else HV
 
     def eval_timed_prepare(self, rf_scale, iters):
         """arm the seeds and build / upload the hipGraph eval_timed(rf_scale, iters) replays (nothing timed)"""

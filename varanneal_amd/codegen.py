@@ -218,7 +218,7 @@ def _printer():
 
         def _print_Symbol(self, s):
             n = s.name
-            for pre, arr in (("x", "x"), ("p", "p"), ("st", "st"), ("sv", "s")):
+            for pre, arr in (("x", "x"), ("p", "p"), ("st", "st"), ("sv", "s"), ("vt", "v"), ("qt", "q")):
                 if n.startswith(pre) and n[len(pre):].isdigit():
                     return "%s[%s]" % (arr, n[len(pre):])
             return n
@@ -274,6 +274,120 @@ def _switch_flat(out, exprs, syms, D, NP, pr, sv):
     out.append("        default: break;")
     out.append("        }")
     out.append("    }")
+    # second order (csrc/va_hvp.h): fdot = J v + (df/dp) q, K_j = sum_i s_i d(fdot_i)/dx_j, acc[k] += s_i d(fdot_i)/dp_k
+    fdot, K, PG2 = second_order_exprs(exprs, syms, D, NP)
+    out.append("    static VA_HD double jvp(%s)" % _SIG_JVP)
+    out.append("    {")
+    out.append("        (void)x; (void)v; (void)q; (void)p; (void)t; (void)st;")
+    out.append("        switch (i) {")
+    for i, e in enumerate(fdot):
+        out.append("        case %d: { %s }" % (i, _emit_case(pr, e, "return %s;")))
+    out.append("        default: return 0.0;")
+    out.append("        }")
+    out.append("    }")
+    out.append("    static VA_HD double vjp2(%s)" % _SIG_VJP2)
+    out.append("    {")
+    out.append("        (void)x; (void)s; (void)v; (void)q; (void)p; (void)t; (void)st;")
+    out.append("        switch (j) {")
+    for j in range(D):
+        if K[j] != 0:
+            out.append("        case %d: { %s }" % (j, _emit_case(pr, K[j], "return %s;")))
+    out.append("        default: return 0.0;")
+    out.append("        }")
+    out.append("    }")
+    out.append("    static VA_HD void pgrad2(%s)" % _SIG_PGRAD2)
+    out.append("    {")
+    out.append("        (void)x; (void)s; (void)v; (void)q; (void)p; (void)t; (void)st; (void)acc;")
+    out.append("        switch (i) {")
+    for i in range(D):
+        stm = ["{ %s }" % _emit_case(pr, PG2[i][k], "acc[%d] += %%s;" % k) for k in range(NP) if PG2[i][k] != 0]
+        if stm:
+            out.append("        case %d: { %s break; }" % (i, " ".join(stm)))
+    out.append("        default: break;")
+    out.append("        }")
+    out.append("    }")
+
+
+_SIG_JVP = "const double *x, const double *v, const double *q, int i, int, const double *p, double t, const double *st"
+_SIG_VJP2 = "const double *x, const double *s, const double *v, const double *q, int j, int, const double *p, double t, const double *st"
+_SIG_PGRAD2 = ("const double *x, const double *s, const double *v, const double *q, int i, int, const double *p, double t, "
+               "const double *st, double *acc")
+
+
+def _tangent_symbols(D, NP):
+    sp = _sympy()
+    return (sp.symbols("vt0:%d" % D, real=True), sp.symbols("qt0:%d" % max(NP, 1), real=True)[:NP],
+            sp.symbols("sv0:%d" % D, real=True))
+
+
+def _fdot(e, xs, ps, vt, qt):
+    """the tangent of one component along (v, q): only its non-zero first derivatives are formed"""
+    sp = _sympy()
+    free = e.free_symbols
+    tot = sp.Integer(0)
+    for k, x in enumerate(xs):
+        if x in free:
+            tot += sp.diff(e, x) * vt[k]
+    for l, p in enumerate(ps):
+        if p in free:
+            tot += sp.diff(e, p) * qt[l]
+    return tot
+
+
+def second_order_exprs(exprs, syms, D, NP):
+    """(fdot[D], K[D], PG2[D][NP]) in the symbols x, p, st, t and vt (state tangent), qt (parameter tangent), sv (adjoint):
+    what the flat struct's jvp, vjp2 and pgrad2 compute (the per-component form)"""
+    sp = _sympy()
+    key = (tuple(exprs), D, NP)
+    if _second_order_memo.get("key") == key:               # (the check and the emitter ask for the same lists)
+        return _second_order_memo["value"]
+    xs, ps = list(syms["x"]), list(syms["p"])
+    vt, qt, sv = _tangent_symbols(D, NP)
+    fdot = [_fdot(e, xs, ps, vt, qt) for e in exprs]
+    K = []
+    for j in range(D):
+        K.append(sum((sv[i] * sp.diff(fdot[i], xs[j]) for i in range(D) if xs[j] in fdot[i].free_symbols), sp.Integer(0)))
+    PG2 = [[(sv[i] * sp.diff(fdot[i], ps[k]) if ps[k] in fdot[i].free_symbols else sp.Integer(0)) for k in range(NP)] for i in range(D)]
+    _second_order_memo.update(key=key, value=(fdot, K, PG2))
+    return fdot, K, PG2
+
+
+_second_order_memo = {}
+
+
+def _uniform_second_order(exprs, syms, D, NP):
+    """the pieces _uniform_flat prints for a translation-invariant model: fd0 (the tangent of component 0), its non-zero
+    derivatives [(o, d fd0 / d x_o)] at the cyclic offsets o that f_0 reads, and [d fd0 / d p_k]"""
+    sp = _sympy()
+    xs, ps = list(syms["x"]), list(syms["p"])
+    vt, qt, _ = _tangent_symbols(D, NP)
+    rel = lambda j: ((j + D // 2) % D) - D // 2
+    f0 = exprs[0]
+    used = sorted(rel(j) for j in range(D) if f0.has(xs[j]))
+    fd0 = _fdot(f0, xs, ps, list(vt), list(qt))
+    dx = [(o, sp.diff(fd0, xs[o % D])) for o in used]
+    return fd0, [(o, d) for o, d in dx if d != 0], [sp.diff(fd0, ps[k]) for k in range(NP)]
+
+
+def uniform_second_order_exprs(exprs, syms, D, NP, rows):
+    """what the translation-invariant struct's one-body jvp / vjp2 / pgrad2 compute at the components `rows`, written out:
+    the pieces of _uniform_second_order shifted cyclically the way the printer shifts them.  (fdot, K, PG2) as dicts by row"""
+    sp = _sympy()
+    xs = list(syms["x"])
+    vt, qt, sv = _tangent_symbols(D, NP)
+    fd0, dx, dp = _uniform_second_order(exprs, syms, D, NP)
+
+    def shift(e, i):
+        m = {}
+        for k in range(D):
+            m[xs[k]] = xs[(k + i) % D]
+            m[vt[k]] = vt[(k + i) % D]
+        return e.xreplace(m)
+    fdot = {i: shift(fd0, i) for i in rows}
+    # column j: row i = j - o holds the residual whose f reads x_j at offset o
+    K = {j: sum((sv[(j - o) % D] * shift(d, j - o) for o, d in dx), sp.Integer(0)) for j in rows}
+    PG2 = {i: [sv[i] * shift(d, i) for d in dp] for i in rows}
+    return fdot, K, PG2
 
 
 def _uniform_flat(exprs, syms, D, NP, pr0):
@@ -289,12 +403,16 @@ def _uniform_flat(exprs, syms, D, NP, pr0):
     used = sorted(rel(j) for j in range(D) if f0.has(xs[j]))
     base = pr0.__class__
 
+    vts, qts, _ = _tangent_symbols(D, NP)
+    vts = list(vts)
+
     def printer(var, shift):
         class P(base):
             def _print_Symbol(self, sym):
-                if sym in xs:
-                    k = rel(xs.index(sym)) - shift
-                    return "x[%s]" % var if k == 0 else "x[w(%s %s %d)]" % (var, "+" if k > 0 else "-", abs(k))
+                for arr, group in (("x", xs), ("v", vts)):
+                    if sym in group:
+                        k = rel(group.index(sym)) - shift
+                        return "%s[%s]" % (arr, var) if k == 0 else "%s[w(%s %s %d)]" % (arr, var, "+" if k > 0 else "-", abs(k))
                 return base._print_Symbol(self, sym)
         return P()
     out = ["    // translation-invariant: one body for every component, neighbours at cyclic offsets %s" % used,
@@ -320,6 +438,27 @@ def _uniform_flat(exprs, syms, D, NP, pr0):
             "        (void)x; (void)s; (void)i; (void)p; (void)t; (void)st; (void)acc;"]
     for k in range(NP):
         dk = sp.diff(f0, ps[k])
+        if dk != 0:
+            out.append("        { %s }" % _emit_case(printer("i", 0), sp.Symbol("SADJ") * dk, "acc[%d] += %%s;" % k).replace("SADJ", "s[i]"))
+    out.append("    }")
+    # second order (csrc/va_hvp.h), the same way: one body, the tangent v read at the offsets x is read at
+    fd0, dx2, dp2 = _uniform_second_order(exprs, syms, D, NP)
+    out += ["    static VA_HD double jvp(%s)" % _SIG_JVP,
+            "    {",
+            "        (void)x; (void)v; (void)q; (void)i; (void)p; (void)t; (void)st;",
+            "        " + _emit_case(printer("i", 0), fd0, "return %s;"),
+            "    }",
+            "    static VA_HD double vjp2(%s)" % _SIG_VJP2,
+            "    {",
+            "        (void)x; (void)s; (void)v; (void)q; (void)j; (void)p; (void)t; (void)st; double r = 0.0;"]
+    for o, dk in dx2:
+        sname = "s[j]" if o == 0 else "s[w(j %s %d)]" % ("-" if o > 0 else "+", abs(o))
+        out.append("        { %s }" % _emit_case(printer("j", o), sp.Symbol("SADJ") * dk, "r += %s;").replace("SADJ", sname))
+    out += ["        return r;", "    }",
+            "    static VA_HD void pgrad2(%s)" % _SIG_PGRAD2,
+            "    {",
+            "        (void)x; (void)s; (void)v; (void)q; (void)i; (void)p; (void)t; (void)st; (void)acc;"]
+    for k, dk in enumerate(dp2):
         if dk != 0:
             out.append("        { %s }" % _emit_case(printer("i", 0), sp.Symbol("SADJ") * dk, "acc[%d] += %%s;" % k).replace("SADJ", "s[i]"))
     out.append("    }")
@@ -363,7 +502,7 @@ def generate_header(exprs, syms, D, NP, nstim, name="user", col=None, ghost=None
             _switch_flat(out, exprs, syms, D, NP, pr, sv)
     out.append("};")
     if NP <= MAX_NP:
-        out.append("#define VA_USER_FLAT 1       // the flat struct is complete: the module also carries the predictor (va_predict.h)")
+        out.append("#define VA_USER_FLAT 1       // the flat struct is complete: the module also carries the predictor (va_predict.h) and the Hessian-vector kernel (va_hvp.h)")
     if col is not None:
         out.append("// the same model in column form (codegen.column_form): %s"
                    % ("translation-invariant stencil, offsets %s" % col["offsets"] if col["uniform"] else "dense, switch on the column"))
@@ -785,6 +924,69 @@ def check_against(f, exprs, syms, D, NP, nstim, stim_ndim=1, trials=3, rtol=1e-1
                                  "(does it branch on its inputs?): %s vs %s" % (got, want[r]))
 
 
+def check_second_order(exprs, syms, D, NP, nstim, trials=2, rtol=1e-10):
+    """The expressions the flat struct's jvp / vjp2 / pgrad2 are printed from, evaluated at random points when a module is
+    made, in the form the struct will have (generate_header's choice):
+      per-component (switch) form   second_order_exprs, every component: fdot against the complex step of the traced f
+                                    along (v, q); K and the summed pgrad2 against the complex step of sum_i s_i fdot_i
+      translation-invariant form    uniform_second_order_exprs -- component 0's pieces shifted cyclically as the printer
+                                    shifts them -- at up to 8 components (the ends of the ring among them): fdot against the
+                                    complex step of f; K_j and pgrad2 against SymPy derivatives of the components
+                                    themselves (no shift involved)
+    Returns the form checked ('switch' / 'uniform'), or None for a model with kinks (Piecewise, Abs, sign: no complex step) --
+    the only modules whose second-order functions go unchecked here; tests/test_hvp_cpu.py compiles the emitted text."""
+    sp = _sympy()
+    if any(e.has(sp.Piecewise, sp.Abs, sp.sign) for e in exprs):
+        return None
+    vt, qt, sv = _tangent_symbols(D, NP)
+    xs, ps = list(syms["x"]), list(syms["p"])
+    rest = list(syms["st"]) + [syms["t"]]
+    uniform = D >= 8 and _translation_invariant(exprs, xs, D)
+    f_fn = sp.lambdify(xs + ps + rest, exprs, modules="numpy")
+    a1 = xs + ps + rest + list(vt) + list(qt)
+    a2 = a1 + list(sv)
+    rng = np.random.RandomState(20260103)
+    h = 1e-30
+    asf = lambda a: np.array([complex(v) for v in a])
+
+    def close(got, want, what):
+        scale = max(np.abs(want).max(), 1e-300) if len(want) else 1.0
+        if len(want) and np.abs(got - want).max() > rtol * scale:
+            raise ValueError("generated %s disagree(s) with the model's derivatives: %s vs %s" % (what, got, want))
+    if uniform:
+        rows = sorted(set(range(D)) if D <= 8 else {0, 1, 2, D // 2, D - 3, D - 2, D - 1, int(rng.randint(3, D - 3))})
+        ufd, uK, uPG = uniform_second_order_exprs(exprs, syms, D, NP, rows)
+        own = {i: _fdot(exprs[i], xs, ps, vt, qt) for i in range(D) if any(xs[j] in exprs[i].free_symbols for j in rows) or i in rows}
+        rK = [sum((sv[i] * sp.diff(fd, xs[j]) for i, fd in own.items() if xs[j] in fd.free_symbols), sp.Integer(0)) for j in rows]
+        rPG = [sv[i] * sp.diff(own[i], ps[k]) for i in rows for k in range(NP)]
+        fd_fn = sp.lambdify(a1, [ufd[i] for i in rows], modules="numpy")
+        u_fn = sp.lambdify(a2, [uK[j] for j in rows] + [uPG[i][k] for i in rows for k in range(NP)], modules="numpy")
+        r_fn = sp.lambdify(a2, rK + rPG, modules="numpy")
+    else:
+        fdot, K, PG2 = second_order_exprs(exprs, syms, D, NP)
+        rows = list(range(D))
+        fd_fn = sp.lambdify(a1, fdot, modules="numpy")
+        u_fn = sp.lambdify(a2, K + [sum((PG2[i][k] for i in range(D)), sp.Integer(0)) for k in range(NP)], modules="numpy")
+    for _ in range(trials):
+        x, p = rng.rand(D) * 0.8 + 0.1, rng.rand(NP) * 0.8 + 0.6
+        r = list(rng.randn(nstim)) + [rng.rand()]
+        v, q, s = rng.randn(D), rng.randn(NP), rng.randn(D)
+        want = asf(f_fn(*(list(x + 1j * h * v) + list(p + 1j * h * q) + r))).imag / h
+        close(asf(fd_fn(*(list(x) + list(p) + r + list(v) + list(q)))).real, want[rows], "jvp")
+        got2 = asf(u_fn(*(list(x) + list(p) + r + list(v) + list(q) + list(s)))).real
+        if uniform:
+            want2 = asf(r_fn(*(list(x) + list(p) + r + list(v) + list(q) + list(s)))).real
+        else:
+            want2 = np.empty(D + NP)
+            for j in range(D + NP):
+                z = np.concatenate([x, p]).astype(complex)
+                z[j] += 1j * h
+                want2[j] = np.dot(s, asf(fd_fn(*(list(z) + r + list(v) + list(q)))).imag) / h
+        close(got2[:len(rows)], want2[:len(rows)], "vjp2")
+        close(got2[len(rows):], want2[len(rows):], "pgrad2")
+    return "uniform" if uniform else "switch"
+
+
 BUILD_TAG = "sched=iterative-maxocc"      # part of every module's cache key: a flag change rebuilds them
 
 
@@ -792,6 +994,7 @@ def _core_fingerprint():
     h = hashlib.sha1(BUILD_TAG.encode())
     for fn in ("va_core.h", "va_device.h", "va_eval_flat.h", "va_eval3.h", "va_eval4.h", "va_epilogue.h", "va_tile2.h", "va_tile3.h",
                "va_tile4.h", "va_tile5.h", "va_eval5.h", "va_persist.h", "va_persist_geo.h", "va_measure.h", "va_predict.h", "va_predict_geo.h",
+               "va_hvp.h", "va_hvp_geo.h",
                "va_user_rhs.hip"):
         with open(os.path.join(CSRC, fn), "rb") as fh:
             h.update(fh.read())
@@ -895,6 +1098,8 @@ def module_for(f, D, NP, nstim=0, stim_ndim=1, verbose=False, p_rows=False, col_
     # no column-run kernel for this model: a dense constant linear part goes to the matrix cores
     lin = (linear_split(exprs, syms, D) if (linear and col is None and ghost is None and colp is None and not p_rows
                                              and NP <= MAX_NP_TUNED) else None)
+    if NP <= MAX_NP:                       # the flat struct's second-order functions (of the rest, when a linear part was split off)
+        check_second_order(exprs if lin is None else lin[1], syms, D, NP, nstim)
     text = generate_header(exprs, syms, D, NP, nstim, getattr(f, "__name__", "f"), col=col, ghost=ghost, lin=lin, colp=colp)
     so, hdr = build_module(text, verbose, variant, compile)
     return dict(so=so, header=hdr, exprs=exprs, text=text, col=col, ghost=ghost, col_variant=variant,

@@ -38,6 +38,7 @@
 #include "va_eval_flat.h"
 #include "va_persist.h"
 #include "va_predict.h"
+#include "va_hvp.h"
 
 using namespace va;
 
@@ -78,6 +79,7 @@ struct UserRhs {
     std::string path;
     void *dl = nullptr;
     RhsTable table = {};       // the module's launchers and sizes (va_user_rhs_table)
+    HvpTable hvp = {};         // ... and the Hessian-vector kernel's (va_user_hvp_table); hvp.hvp NULL: the module has none
     // variant.n_colp_vectors > 0: the column-run instantiation is of the model's column-parameter form (RhsUserColP); its map
     // (va_user_colp_map): shared scalars S, vectors V, then the global index of each shared scalar and of each vector entry
     std::vector<int> colp;
@@ -97,6 +99,7 @@ struct va_problem_s {
     Dev dv;
     int device = 0, rhs = 0, keep_paths = 0;
     RhsTable rt = {};                  // the right-hand side's launchers (a copy; eval: the kernel THIS handle runs)
+    HvpTable rt_hvp = {};              // the Hessian-vector kernel's launcher (va_hvp.h), hvp NULL: none
     NnetActLaunch nn_act = nullptr;    // generated activation module's launcher (nn.act >= NNET_USER)
     // few seeds, short paths: the whole ladder in ONE launch, every vector of the minimisation resident in
     // the LDS of pz_G workgroups per seed (va_persist.h); chosen at create when the slices fit and all are co-resident
@@ -587,6 +590,7 @@ int plan_problem(va_handle h, const va_problem_desc *d, const UserRhs *user, Eva
     h->rhs = d->rhs;
     if (!user) {
         builtin_rhs_table(h->rt);
+        builtin_hvp_table(h->rt_hvp);
         EvalForm l96;
         l96.ne = RhsL96s::NE; l96.ghost = RhsL96g::GHOST; l96.has_reach5 = true;
         l96.reach5[0] = t5_xl<RhsL96s>(); l96.reach5[1] = t5_xr<RhsL96s>(); l96.reach5[2] = t5_gl<RhsL96s>(); l96.reach5[3] = t5_gr<RhsL96s>();
@@ -597,6 +601,7 @@ int plan_problem(va_handle h, const va_problem_desc *d, const UserRhs *user, Eva
     TRY(plan_module(d, *user, mp));
     plan = mp.plan;
     h->rt = user->table;
+    h->rt_hvp = user->hvp;
     if (mp.variant) h->rt.eval = user->table.eval_var;
     dv.dm.lin = user->variant.has_linear;
     dv.cps = mp.cps; dv.cpv = mp.cpv;
@@ -956,6 +961,14 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
         return fail(VA_EINVAL, "%s was built against different headers (table %d vs %zu bytes, Dev %d vs %zu bytes): rebuild it", path,
                     table_bytes, sizeof(RhsTable), t.dev_bytes, sizeof(Dev));
     }
+    typedef int (*hvp_fn)(HvpTable *, int);
+    if (hvp_fn hv = (hvp_fn)dlsym(u.dl, "va_user_hvp_table")) {
+        const int hb = hv(&u.hvp, (int)sizeof(HvpTable));
+        if (hb != (int)sizeof(HvpTable) || u.hvp.hvp_bytes != (int)sizeof(HvpArgs)) {
+            dlclose(u.dl);
+            return fail(VA_EINVAL, "%s was built against different headers (HvpTable %d vs %zu bytes): rebuild it", path, hb, sizeof(HvpTable));
+        }
+    }
     if (info_fn vinfo = (info_fn)dlsym(u.dl, "va_user_variant_info")) {
         int uv[UV_N];
         vinfo(uv);
@@ -1202,6 +1215,65 @@ int va_predict(va_handle h, const double *x0, const double *p, int32_t T, double
         return fail(VA_EHIP, "k_predict launch: %s", hipGetErrorString(e));
     }
     HIPCHK(hipMemcpyAsync(out, out_d, sizeof(double) * no, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    return VA_OK;
+}
+
+// Hessian-vector products of the action at npts points along nvec directions each (va_hvp.h): HV = (d^2 A / dXP^2) V, or the
+// Gauss-Newton part of it.  Works on buffers of its own, like va_predict: the handle's resident paths, seed states and
+// captured graphs are not touched.  The handle's bounds play no part: this is the Hessian of the unconstrained action.
+int va_hess_vec(va_handle h, const double *XP, const double *P, const double *V, int32_t npts, int32_t nvec, int64_t ld,
+                double rf_scale, int32_t gauss_newton, int32_t tile_rows, double *HV)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    if (!XP || !V || !HV) return fail(VA_EINVAL, "XP / V / HV must not be NULL");
+    if (npts < 1 || nvec < 1) return fail(VA_EINVAL, "npts and nvec must be at least 1 (npts=%d nvec=%d)", npts, nvec);
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "va_hess_vec: the network action has no second derivatives here (ODE handles only)");
+    const Dev &dv = h->dv;
+    const Dims &hd = dv.dm;
+    if (hd.tdp) return fail(VA_EUNSUPPORTED, "va_hess_vec: time-dependent parameters are not carried");
+    if (dv.pp.rm_full || dv.pp.rf0_full)
+        return fail(VA_EUNSUPPORTED, "va_hess_vec: full %s matrices (kind 2) are not carried: scalar or per-entry weights only", dv.pp.rm_full ? "RM" : "RF");
+    if (hd.lin) return fail(VA_EUNSUPPORTED, "va_hess_vec: the module's dense linear part was split off (LINEAR): build it with linear=False");
+    if (!h->rt_hvp.hvp)
+        return fail(VA_EUNSUPPORTED, "va_hess_vec: the model has no flat form f(x, i, p) to differentiate (more than %d parameters: "
+                                     "its module carries the column-parameter form only)", RHS_BIG_NP);
+    const int64_t n_var = (int64_t)hd.ND + hd.NPest;
+    if (ld < n_var) return fail(VA_EINVAL, "ld < n_var (%lld < %lld)", (long long)ld, (long long)n_var);
+    if (hd.NPt > 0 && !P) return fail(VA_EINVAL, "P must not be NULL (the model has %d parameter(s))", hd.NPt);
+    if (tile_rows < 0) return fail(VA_EINVAL, "tile_rows %d", tile_rows);
+    HvpGeo geo;
+    if (!plan_hvp(hd.D, hd.N, hd.disc, hd.NPt, npts, nvec, tile_rows, geo)) {
+        if (hd.D > geo.maxD && geo.maxD > 0)
+            return fail(VA_EUNSUPPORTED, "va_hess_vec: D=%d: %s (at most D=%d with this discretisation)", hd.D, geo.why, geo.maxD);
+        return fail(tile_rows > 0 ? VA_EINVAL : VA_EUNSUPPORTED, "va_hess_vec: %s (tile_rows=%d, at most %d)", geo.why, tile_rows, geo.Tmax);
+    }
+    HvpArgs a;
+    a.dm = hd; a.dm.T = geo.T; a.dm.ntiles = geo.ntiles; a.dm.bounded = 0; a.dm.B = npts;
+    a.pp = dv.pp; a.pp.lo = a.pp.hi = nullptr;
+    a.npts = npts; a.nvec = nvec; a.ld = (long)ld; a.gn = gauss_newton ? 1 : 0;
+    a.rm_ld = hd.emode == 5 ? dv.g5.LY : hd.L;              // (the streaming kernel pads its observation rows)
+    a.c = 2.0 * rf_scale * hd.cfe;
+    HIPCHK(hipSetDevice(h->device));
+    // one allocation: [X | P | V | HV | partial parameter rows]
+    const size_t nx = (size_t)npts * ld, np = (size_t)npts * hd.NPt, nv = (size_t)npts * nvec * ld,
+                 npart = (size_t)npts * nvec * geo.ntiles * hd.NPt;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (nx + np + 2 * nv + npart + 1)));
+    struct Free { double *q; ~Free() { (void)hipFree(q); } } guard{buf};
+    double *x_d = buf, *p_d = x_d + nx, *v_d = p_d + np, *hv_d = v_d + nv, *part_d = hv_d + nv;
+    HIPCHK(hipMemcpyAsync(x_d, XP, sizeof(double) * nx, hipMemcpyHostToDevice, h->stream));
+    if (np) HIPCHK(hipMemcpyAsync(p_d, P, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(v_d, V, sizeof(double) * nv, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(hv_d, 0, sizeof(double) * nv, h->stream));      // (the padding between n_var and ld)
+    a.X = x_d; a.pp.Pfull = p_d; a.V = v_d; a.HV = hv_d; a.part = part_d;
+    const hipError_t e = h->rt_hvp.hvp(a, geo.lds_bytes, h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
+        return fail(VA_EHIP, "k_hvp launch: %s", hipGetErrorString(e));
+    }
+    HIPCHK(hipMemcpyAsync(HV, hv_d, sizeof(double) * nv, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
     return VA_OK;

@@ -166,6 +166,29 @@ struct RhsL96 {
     {
         acc[0] += s[i];
     }
+    // second order (va_hvp.h); q: the full-length parameter tangent.  fdot_i = (J v)_i + (df_i/dp) q
+    static VA_HD double jvp(const double *x, const double *v, const double *q, int i, int D, const double *, double, const double *)
+    {
+        int im1 = i == 0 ? D - 1 : i - 1;
+        int im2 = im1 == 0 ? D - 1 : im1 - 1;
+        int ip1 = i == D - 1 ? 0 : i + 1;
+        return v[im1] * (x[ip1] - x[im2]) + x[im1] * (v[ip1] - v[im2]) - v[i] + q[0];
+    }
+    // K_j = sum_i s_i d(fdot_i)/dx_j: f is bilinear in x, so this is J(v)^T s without the linear term's -s_j
+    static VA_HD double vjp2(const double *, const double *s, const double *v, const double *, int j, int D, const double *, double,
+                             const double *)
+    {
+        int jm1 = j == 0 ? D - 1 : j - 1;
+        int jm2 = jm1 == 0 ? D - 1 : jm1 - 1;
+        int jp1 = j == D - 1 ? 0 : j + 1;
+        int jp2 = jp1 == D - 1 ? 0 : jp1 + 1;
+        return s[jp1] * (v[jp2] - v[jm1]) + s[jm1] * v[jm2] - s[jp2] * v[jp1];
+    }
+    // acc[k] += s_i d(fdot_i)/dp_k: the forcing enters linearly, nothing to add
+    static VA_HD void pgrad2(const double *, const double *, const double *, const double *, int, int, const double *, double,
+                             const double *, double *)
+    {
+    }
 };
 
 // ---------------------------------------------------------------- tile context

@@ -122,6 +122,7 @@ inline void with_disc(int disc, F &&f)
 // Everything the host launches that depends on the right-hand side.  The built-in Lorenz-96 fills one in va_kernels.hip
 // (builtin_rhs_table); a generated module fills one through its only entry point, va_user_rhs_table (va_user_rhs.hip).
 struct PredictArgs;
+struct HvpArgs;
 struct RhsTable {
     int bytes;                                 // sizeof(RhsTable), then the sizes of what crosses the boundary by value or by layout
     int dev_bytes, seed_bytes, predict_bytes;
@@ -132,6 +133,14 @@ struct RhsTable {
     hipError_t (*predict)(const PredictArgs &, hipStream_t);      // the RK4 predictor (va_predict.h), or NULL
 };
 void builtin_rhs_table(RhsTable &t);
+// The launcher slot of the Hessian-vector kernel (va_hvp.h).  A table of its own beside RhsTable, whose layout modules and
+// their checks already agree on: the built-in fills one in va_kernels.hip (builtin_hvp_table), a generated module through
+// a second entry point, va_user_hvp_table (va_user_rhs.hip); a module without that entry point has no such kernel.
+struct HvpTable {
+    int bytes, hvp_bytes;                      // sizeof(HvpTable), sizeof(HvpArgs)
+    hipError_t (*hvp)(const HvpArgs &, size_t lds_bytes, hipStream_t);      // or NULL
+};
+void builtin_hvp_table(HvpTable &t);
 
 // launch wrappers (va_kernels.hip); all asynchronous on `s`
 void launch_ls(const Dev &dv, hipStream_t s);

@@ -416,6 +416,103 @@ class Annealer(LadderAnnealer):
         diff = pred[..., 1:, self.Lidx] - Yf[1:]
         return np.sqrt(np.mean(diff * diff, axis=(-2, -1)))
 
+    # ------------------------------------------------------------------ second derivatives at the minimisers
+    def _minimiser(self, beta, seed):
+        """(xp [n_var], P [NP], rf_scale) of the stored minimiser of (seed, rung)"""
+        if self._pb is None or not getattr(self, "initalized", False):
+            raise ValueError("second derivatives are taken at the minimisers: call anneal() first")
+        if self._tdp:
+            raise NotImplementedError("hess_vec: time-dependent parameters are not carried")
+        sb, kb = self._select([beta], [seed] if self._batched else None)
+        row = self._mp[sb[0], kb[0]]
+        P = np.array(row[self._NX:])
+        return np.concatenate([row[:self._NX], P[self.Pidx]]), P, float(self._rf_scale[kb[0]])
+
+    def hess_vec(self, V, beta=-1, seed=0, gauss_newton=False):
+        """(d^2 A / d[X | p_est]^2) V at the stored minimiser of (seed, rung beta), with that rung's RF, on the device
+        (csrc/va_hvp.h).  V: (n_var,) or (nvec, n_var), packed like the path vector.  gauss_newton: 2 J^T W J only."""
+        xp, P, rf = self._minimiser(beta, seed)
+        V = np.asarray(V, dtype=np.float64)
+        out = self._pb.hess_vec(xp[None, :], V.reshape(1, -1, xp.size), rf, P=P[None, :], gauss_newton=gauss_newton)[0]
+        return out[0] if V.ndim == 1 else out
+
+    def _hessian_blocks(self, beta, seed, gauss_newton):
+        """(ab, H_xp, H_pp): the path block in SciPy's upper banded layout (ab[u + i - j, j] = H[i, j], u = (hb + 1) D - 1
+        superdiagonals), the border (N D, NPest) and the parameter block.  ONE batched call of (2 hb + 1) D + NPest
+        directions: the Hessian couples time rows at most hb apart (hb = 1; 2 for Simpson-Hermite), so the rows n with
+        equal n mod (2 hb + 1) are probed together -- coloured direction c has ones at all path entries (n, j) with
+        (n mod (2 hb + 1)) D + j == c -- plus one unit direction per estimated parameter."""
+        N, D, NPe = self.N_model, self.D, self.NPest
+        hb = 2 if self.disc_name == "SimpsonHermite" else 1
+        nc, ND = 2 * hb + 1, N * D
+        V = np.zeros((nc * D + NPe, ND + NPe))
+        rows = np.arange(N)
+        for c in range(nc * D):
+            V[c, (rows[rows % nc == c // D]) * D + c % D] = 1.0
+        V[nc * D + np.arange(NPe), ND + np.arange(NPe)] = 1.0
+        HV = self.hess_vec(V, beta=beta, seed=seed, gauss_newton=gauss_newton)
+        u = (hb + 1) * D - 1
+        ab = np.zeros((u + 1, ND))
+        for n in range(N):
+            for j in range(D):
+                col = HV[(n % nc) * D + j]                     # column (n, j) of H on the rows within hb of n
+                lo = max(0, n - hb) * D
+                i = np.arange(lo, n * D + j + 1)               # upper triangle
+                ab[u + i - (n * D + j), n * D + j] = col[i]
+        H_xp = HV[nc * D:, :ND].T.copy()                       # (the parameter rows of the coloured products are discarded)
+        H_pp = HV[nc * D:, ND:].copy()
+        return ab, H_xp, 0.5 * (H_pp + H_pp.T)
+
+    def action_hessian(self, beta=-1, seed=0, gauss_newton=False, form='dense'):
+        """The Hessian of the action at the stored minimiser of (seed, rung), assembled from one batched device call
+        (see hess_vec).  form='banded': (ab, H_xp, H_pp) with ab in SciPy's upper banded layout; form='dense': the
+        (n_var, n_var) matrix (ValueError past 2 GiB)."""
+        if form not in ('dense', 'banded'):
+            raise ValueError("form must be 'dense' or 'banded'")
+        n = self.N_model * self.D + self.NPest
+        if form == 'dense' and 8.0 * n * n > 2.0 * 1024 ** 3:
+            raise ValueError("the dense Hessian of %d variables takes %.1f GiB (> 2 GiB): ask for form='banded'"
+                             % (n, 8.0 * n * n / 1024 ** 3))
+        ab, H_xp, H_pp = self._hessian_blocks(beta, seed, gauss_newton)
+        if form == 'banded':
+            return ab, H_xp, H_pp
+        ND, u = self.N_model * self.D, ab.shape[0] - 1
+        H = np.zeros((n, n))
+        for k in range(u + 1):                                # superdiagonal k
+            d = ab[u - k, k:]
+            H[np.arange(ND - k), np.arange(k, ND)] = d
+            H[np.arange(k, ND), np.arange(ND - k)] = d
+        H[:ND, ND:] = H_xp
+        H[ND:, :ND] = H_xp.T
+        H[ND:, ND:] = H_pp
+        return H
+
+    def param_covariance(self, beta=-1, seeds=None, gauss_newton=False):
+        """Laplace approximation of the estimated parameters' covariance at the stored minimisers: the parameter block
+        of the inverse Hessian, (H_pp - H_px H_xx^-1 H_xp)^-1, with H_xx factored in banded form (SciPy).  It is the
+        inverse Hessian of the action AS THE PACKAGE NORMALISES IT (measurement term / (L N_data), model term /
+        (D (N - 1))): for a negative log-likelihood A' = c A the covariance is this one divided by c.
+        Returns (NPest, NPest), or (B_sel, NPest, NPest) for a batch.  numpy.linalg.LinAlgError if H_xx is not positive
+        definite (not at a minimum, or a flat direction): gauss_newton=True is positive semi-definite by construction."""
+        import scipy.linalg as sla
+        sb, _ = self._select(None, seeds)
+        out = []
+        for b in sb:
+            ab, H_xp, H_pp = self._hessian_blocks(beta, int(b), gauss_newton)
+            try:
+                cb = sla.cholesky_banded(ab, lower=False)
+            except np.linalg.LinAlgError as e:
+                raise np.linalg.LinAlgError("the path block of the Hessian (seed %d) is not positive definite (%s): not a minimum, "
+                                            "or a flat direction; gauss_newton=True gives the positive semi-definite part" % (b, e))
+            S = H_pp - np.dot(H_xp.T, sla.cho_solve_banded((cb, False), H_xp))
+            try:
+                out.append(np.linalg.inv(S))
+            except np.linalg.LinAlgError as e:
+                raise np.linalg.LinAlgError("the Schur complement H_pp - H_px H_xx^-1 H_xp (seed %d) is singular (%s): the data do "
+                                            "not determine the estimated parameters at this point" % (b, e))
+        out = np.array(out)
+        return out if self._batched else out[0]
+
     def me_gaussian(self, X):
         """Measurement error of a path (va_ode.py:138-158); X may omit the parameters."""
         X = np.asarray(X, dtype=np.float64)
