@@ -36,6 +36,9 @@ def main():
                     help="hold the last N observations back and report the forecast error per rung")
     ap.add_argument("--errorbars", action="store_true",
                     help="print the final k +- sigma per seed (Laplace approximation: Annealer.param_covariance)")
+    ap.add_argument("--statebars", action="store_true",
+                    help="print the RMS sigma of the observed and of the unobserved columns at the last rung, and log det H, "
+                         "per seed (Laplace approximation on the device: Annealer.laplace)")
     args = ap.parse_args()
 
     D = 20
@@ -104,6 +107,20 @@ def main():
         cov = cov.reshape(-1, 1, 1)
         for b, kk in enumerate(np.ravel(np.asarray(anneal1.minpaths)[..., -1, N_model * D])):
             print("seed %d   k = %.4f +- %.2e" % (b, kk, np.sqrt(cov[b, 0, 0])))
+
+    if args.statebars:
+        # marginal variances of every state from the selected inverse of the Hessian (Gauss-Newton where the exact one is
+        # not positive definite: status != 0), and the Laplace log-determinant that ranks seeds by evidence
+        lap = anneal1.laplace(beta=-1)
+        if np.any(lap["status"] != 0):
+            print("\n(the exact Hessian is not positive definite at %d of %d seeds: Gauss-Newton part)"
+                  % (int(np.sum(lap["status"] != 0)), lap["status"].size))
+            lap = anneal1.laplace(beta=-1, gauss_newton=True)
+        var = lap["state_var"].reshape(-1, N_model, D)
+        unobserved = [j for j in range(D) if j not in Lidx]
+        for b in range(var.shape[0]):
+            print("seed %d   RMS sigma: observed %.3e  unobserved %.3e   log det H = %.4f"
+                  % (b, np.sqrt(np.mean(var[b][:, Lidx])), np.sqrt(np.mean(var[b][:, unobserved])), np.ravel(lap["logdet"])[b]))
 
     anneal1.save_paths(os.path.join(args.out, "paths.npy"))
     anneal1.save_params(os.path.join(args.out, "params.npy"))

@@ -231,6 +231,34 @@ int va_predict(va_handle h, const double *x0, const double *p, int32_t T, double
 int va_hess_vec(va_handle h, const double *XP, const double *P, const double *V, int32_t npts, int32_t nvec, int64_t ld,
                 double rf_scale, int32_t gauss_newton, int32_t tile_rows, double *HV);
 
+/* Selected inverse and log-determinant of npts symmetric positive definite block-tridiagonal matrices with a dense border
+ * (csrc/va_selinv.h: block Cholesky forward, Takahashi's recurrence backward, one workgroup per matrix), on the handle's
+ * device and stream; any handle serves, the blocks are the caller's.  All arrays HOST, C order:
+ *   Dk [npts][K][W][W] diagonal blocks, Bk [npts][K-1][W][W] the blocks under them (H_{k+1,k}), Pk [npts][K][NPe][W] the
+ *   border, Hpp [npts][NPe][NPe]; NPe = 0 is legal (Pk, Hpp unused), Bk unused at K = 1
+ *   Skk, Snk, Spk, Spp: the same blocks of the inverse; any of them NULL: not written
+ *   logdet [npts]; status [npts]: 0 fine, k + 1 a pivot <= 0 or NaN in path block k, -1 in the parameters' Schur complement.
+ *        Every requested output of a failed matrix is NaN, the others are unaffected, the call returns VA_OK.
+ * The same inputs give the same bits on every call.
+ * VA_EUNSUPPORTED: W > 64 or NPe > 32 (reason in va_last_error). */
+int va_blocktri_selinv(va_handle h, int32_t npts, int32_t K, int32_t W, int32_t NPe, const double *Dk, const double *Bk,
+                       const double *Pk, const double *Hpp, double *Skk, double *Snk, double *Spk, double *Spp, double *logdet,
+                       int32_t *status);
+
+/* Laplace approximation at npts points: the inverse of the action's Hessian on its own sparsity pattern and log det H.  Per
+ * point: coloured directions, k_hvp, k_hblocks, k_selinv; only what is asked for comes back.
+ *   XP [npts*ld], P [npts*NP] as in va_hess_vec; rf_scale [npts]: every point its own; gauss_newton as in va_hess_vec
+ *   chunk_pts 0, or the points per chunk: the device workspace of a chunk stays under 1 GiB (csrc/va_selinv_geo.h)
+ *   var_x [npts*N*D] always; cov_xx [npts*N*D*D] the same-time D x D blocks, cov_px [npts*NPest*N*D], cov_pp
+ *        [npts*NPest*NPest]: NULL = not wanted; logdet [npts], status [npts] as in va_blocktri_selinv (blocks of hb = 1 time
+ *        row, 2 with Simpson-Hermite).  A point whose Hessian is not positive definite is NaN with its status set.
+ * Bounds are ignored, resident paths, seed states and captured graphs left alone, as in va_hess_vec.
+ * VA_EINVAL: npts < 1, ld < n_var, a forced chunk that does not fit the workspace.
+ * VA_EUNSUPPORTED: whatever va_hess_vec refuses; D > 64, D > 32 with Simpson-Hermite, more than 32 estimated parameters. */
+int va_laplace(va_handle h, const double *XP, const double *P, int32_t npts, int64_t ld, const double *rf_scale,
+               int32_t gauss_newton, int32_t chunk_pts, double *var_x, double *cov_xx, double *cov_px, double *cov_pp,
+               double *logdet, int32_t *status);
+
 /* Measurement hook for bench.py: `iters` complete S1 evaluations (the same launch va_action_grad
  * makes: A, me, fe and the full gradient are formed every time) on the resident paths (those of
  * the last va_action_grad / va_anneal call), bracketed by HIP events on the handle's stream;

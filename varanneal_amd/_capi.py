@@ -207,6 +207,10 @@ def lib():
     L.va_predict.argtypes = [h, c_dp, c_dp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp]
     L.va_hess_vec.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, c_dp]
     L.va_hess_vec.restype = C.c_int
+    L.va_blocktri_selinv.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [c_dp] * 9 + [c_ip]
+    L.va_blocktri_selinv.restype = C.c_int
+    L.va_laplace.argtypes = [h, c_dp, c_dp, C.c_int32, C.c_int64, c_dp, C.c_int32, C.c_int32] + [c_dp] * 5 + [c_ip]
+    L.va_laplace.restype = C.c_int
     L.va_eval_timed.argtypes = [h, C.c_double, C.c_int32, C.POINTER(C.c_float)]
     L.va_eval_timed_prepare.argtypes = [h, C.c_double, C.c_int32]
     L.va_get_counters.argtypes = [h, c_lp, c_lp, c_lp]
@@ -237,7 +241,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_hess_vec", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -494,6 +498,60 @@ class Problem(object):
         check(self._L.va_hess_vec(self._h, XP.ctypes.data_as(c_dp), P.ctypes.data_as(c_dp), V.ctypes.data_as(c_dp), npts,
                                   V.shape[1], n, float(rf_scale), 1 if gauss_newton else 0, int(tile_rows), HV.ctypes.data_as(c_dp)))
         return HV[0] if one else HV
+
+    def blocktri_selinv(self, Dk, Bk, Pk, Hpp, want=("Skk", "Snk", "Spk", "Spp")):
+        """Selected inverse and log-determinant of npts block-tridiagonal matrices with a dense border, on the device
+        (va_blocktri_selinv; csrc/va_selinv.h).  Dk (npts, K, W, W), Bk (npts, K - 1, W, W) the blocks H_{k+1,k}, Pk
+        (npts, K, NPe, W), Hpp (npts, NPe, NPe); NPe = 0 is legal.  want: which blocks of the inverse come back (the others
+        are not written).  Returns a dict of them plus logdet (npts,) and status (npts,): 0 fine, k + 1 / -1 where a
+        matrix stopped being positive definite (its outputs are NaN)."""
+        Dk = _f64(Dk)
+        npts, K, W = Dk.shape[:3]
+        Hpp = _f64(Hpp).reshape(npts, -1)
+        NPe = int(round(np.sqrt(Hpp.shape[1])))
+        Bk, Pk = _f64(Bk).reshape(npts, K - 1, W, W), _f64(Pk).reshape(npts, K, NPe, W)
+        Hpp = Hpp.reshape(npts, NPe, NPe)
+        out = {}
+        for name, shape in (("Skk", Dk.shape), ("Snk", Bk.shape), ("Spk", Pk.shape), ("Spp", Hpp.shape)):
+            if name in want:
+                out[name] = np.empty(shape)
+        out["logdet"], out["status"] = np.empty(npts), np.empty(npts, np.int32)
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None and a.size else None
+        check(self._L.va_blocktri_selinv(self._h, npts, K, W, NPe, ptr(Dk), ptr(Bk), ptr(Pk), ptr(Hpp), ptr(out.get("Skk")),
+                                         ptr(out.get("Snk")), ptr(out.get("Spk")), ptr(out.get("Spp")),
+                                         out["logdet"].ctypes.data_as(c_dp), out["status"].ctypes.data_as(c_ip)))
+        return out
+
+    def laplace(self, XP, rf_scale, P=None, gauss_newton=False, full=False, chunk_pts=0):
+        """Laplace approximation at the points XP (npts, n_var), each with its own rf_scale (a scalar serves all), on the
+        device (va_laplace): the coloured Hessian-vector products, the block-tridiagonal factor and the selected inverse.
+        P as in hess_vec.  Returns a dict: var_x (npts, N, D), cov_pp (npts, NPest, NPest), logdet, status; with full=True
+        also cov_xx (npts, N, D, D), the same-time blocks, and cov_px (npts, NPest, N D).  A point whose Hessian is not
+        positive definite is NaN with status k + 1 (block k of the path) or -1 (the parameters' Schur complement).
+        chunk_pts: points per chunk of device workspace (0: as many as stay under 1 GiB)."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("laplace: the network action has no second derivatives here (ODE handles only)")
+        n = self.n_var
+        XP = _f64(XP).reshape(-1, n)
+        npts = XP.shape[0]
+        NP, NPe, N, D = self.desc.NP, self.NPest, self.N, self.D
+        if P is None:
+            P = np.ctypeslib.as_array(self.desc.P, shape=(NP,)) if (NP and not self.desc.p_time_dependent) else np.zeros(NP)
+        P = _f64(P).reshape(-1, NP) if NP else np.zeros((npts, 0))
+        if P.shape[0] == 1 and npts > 1:
+            P = np.ascontiguousarray(np.broadcast_to(P, (npts, NP)))
+        if P.shape[0] != npts:
+            raise ValueError("laplace: %d points but %d parameter vectors" % (npts, P.shape[0]))
+        rf = np.ascontiguousarray(np.broadcast_to(_f64(rf_scale).reshape(-1), (npts,)))
+        out = dict(var_x=np.empty((npts, N, D)), cov_pp=np.empty((npts, NPe, NPe)), logdet=np.empty(npts),
+                   status=np.empty(npts, np.int32))
+        if full:
+            out["cov_xx"], out["cov_px"] = np.empty((npts, N, D, D)), np.empty((npts, NPe, N * D))
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
+        check(self._L.va_laplace(self._h, ptr(XP), ptr(P), npts, n, ptr(rf), 1 if gauss_newton else 0, int(chunk_pts),
+                                 ptr(out["var_x"]), ptr(out.get("cov_xx")), ptr(out.get("cov_px")), ptr(out["cov_pp"]),
+                                 ptr(out["logdet"]), out["status"].ctypes.data_as(c_ip)))
+        return out
 
     def eval_timed_prepare(self, rf_scale, iters):
         """arm the seeds and build / upload the hipGraph eval_timed(rf_scale, iters) replays (nothing timed)"""

@@ -39,6 +39,7 @@
 #include "va_persist.h"
 #include "va_predict.h"
 #include "va_hvp.h"
+#include "va_selinv.h"
 
 using namespace va;
 
@@ -1223,22 +1224,47 @@ int va_predict(va_handle h, const double *x0, const double *p, int32_t T, double
 // Hessian-vector products of the action at npts points along nvec directions each (va_hvp.h): HV = (d^2 A / dXP^2) V, or the
 // Gauss-Newton part of it.  Works on buffers of its own, like va_predict: the handle's resident paths, seed states and
 // captured graphs are not touched.  The handle's bounds play no part: this is the Hessian of the unconstrained action.
+// hvp_refusals: what the handle cannot do (`who` names the caller); hvp_on_device: the launch on device buffers
+// (x_d [npts][ld], p_d [npts][NP], v_d / hv_d [npts][nvec][ld], part_d [npts][nvec][ntiles][NP]); va_hess_vec wraps both
+// around host arrays, va_laplace runs them on the chunks of its workspace.
+static int hvp_refusals(va_handle h, const char *who)
+{
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "%s: the network action has no second derivatives here (ODE handles only)", who);
+    const Dev &dv = h->dv;
+    const Dims &hd = dv.dm;
+    if (hd.tdp) return fail(VA_EUNSUPPORTED, "%s: time-dependent parameters are not carried", who);
+    if (dv.pp.rm_full || dv.pp.rf0_full)
+        return fail(VA_EUNSUPPORTED, "%s: full %s matrices (kind 2) are not carried: scalar or per-entry weights only", who, dv.pp.rm_full ? "RM" : "RF");
+    if (hd.lin) return fail(VA_EUNSUPPORTED, "%s: the module's dense linear part was split off (LINEAR): build it with linear=False", who);
+    if (!h->rt_hvp.hvp)
+        return fail(VA_EUNSUPPORTED, "%s: the model has no flat form f(x, i, p) to differentiate (more than %d parameters: "
+                                     "its module carries the column-parameter form only)", who, RHS_BIG_NP);
+    return VA_OK;
+}
+
+static hipError_t hvp_on_device(va_handle h, const HvpGeo &geo, const double *x_d, const double *p_d, const double *v_d, double *hv_d,
+                                double *part_d, int32_t npts, int32_t nvec, int64_t ld, double rf_scale, int32_t gauss_newton)
+{
+    const Dev &dv = h->dv;
+    const Dims &hd = dv.dm;
+    HvpArgs a;
+    a.dm = hd; a.dm.T = geo.T; a.dm.ntiles = geo.ntiles; a.dm.bounded = 0; a.dm.B = npts;
+    a.pp = dv.pp; a.pp.lo = a.pp.hi = nullptr;
+    a.npts = npts; a.nvec = nvec; a.ld = (long)ld; a.gn = gauss_newton ? 1 : 0;
+    a.rm_ld = hd.emode == 5 ? dv.g5.LY : hd.L;              // (the streaming kernel pads its observation rows)
+    a.c = 2.0 * rf_scale * hd.cfe;
+    a.X = x_d; a.pp.Pfull = p_d; a.V = v_d; a.HV = hv_d; a.part = part_d;
+    return h->rt_hvp.hvp(a, geo.lds_bytes, h->stream);
+}
+
 int va_hess_vec(va_handle h, const double *XP, const double *P, const double *V, int32_t npts, int32_t nvec, int64_t ld,
                 double rf_scale, int32_t gauss_newton, int32_t tile_rows, double *HV)
 {
     if (!h) return fail(VA_EINVAL, "null handle");
     if (!XP || !V || !HV) return fail(VA_EINVAL, "XP / V / HV must not be NULL");
     if (npts < 1 || nvec < 1) return fail(VA_EINVAL, "npts and nvec must be at least 1 (npts=%d nvec=%d)", npts, nvec);
-    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "va_hess_vec: the network action has no second derivatives here (ODE handles only)");
-    const Dev &dv = h->dv;
-    const Dims &hd = dv.dm;
-    if (hd.tdp) return fail(VA_EUNSUPPORTED, "va_hess_vec: time-dependent parameters are not carried");
-    if (dv.pp.rm_full || dv.pp.rf0_full)
-        return fail(VA_EUNSUPPORTED, "va_hess_vec: full %s matrices (kind 2) are not carried: scalar or per-entry weights only", dv.pp.rm_full ? "RM" : "RF");
-    if (hd.lin) return fail(VA_EUNSUPPORTED, "va_hess_vec: the module's dense linear part was split off (LINEAR): build it with linear=False");
-    if (!h->rt_hvp.hvp)
-        return fail(VA_EUNSUPPORTED, "va_hess_vec: the model has no flat form f(x, i, p) to differentiate (more than %d parameters: "
-                                     "its module carries the column-parameter form only)", RHS_BIG_NP);
+    TRY(hvp_refusals(h, "va_hess_vec"));
+    const Dims &hd = h->dv.dm;
     const int64_t n_var = (int64_t)hd.ND + hd.NPest;
     if (ld < n_var) return fail(VA_EINVAL, "ld < n_var (%lld < %lld)", (long long)ld, (long long)n_var);
     if (hd.NPt > 0 && !P) return fail(VA_EINVAL, "P must not be NULL (the model has %d parameter(s))", hd.NPt);
@@ -1249,12 +1275,6 @@ int va_hess_vec(va_handle h, const double *XP, const double *P, const double *V,
             return fail(VA_EUNSUPPORTED, "va_hess_vec: D=%d: %s (at most D=%d with this discretisation)", hd.D, geo.why, geo.maxD);
         return fail(tile_rows > 0 ? VA_EINVAL : VA_EUNSUPPORTED, "va_hess_vec: %s (tile_rows=%d, at most %d)", geo.why, tile_rows, geo.Tmax);
     }
-    HvpArgs a;
-    a.dm = hd; a.dm.T = geo.T; a.dm.ntiles = geo.ntiles; a.dm.bounded = 0; a.dm.B = npts;
-    a.pp = dv.pp; a.pp.lo = a.pp.hi = nullptr;
-    a.npts = npts; a.nvec = nvec; a.ld = (long)ld; a.gn = gauss_newton ? 1 : 0;
-    a.rm_ld = hd.emode == 5 ? dv.g5.LY : hd.L;              // (the streaming kernel pads its observation rows)
-    a.c = 2.0 * rf_scale * hd.cfe;
     HIPCHK(hipSetDevice(h->device));
     // one allocation: [X | P | V | HV | partial parameter rows]
     const size_t nx = (size_t)npts * ld, np = (size_t)npts * hd.NPt, nv = (size_t)npts * nvec * ld,
@@ -1267,14 +1287,150 @@ int va_hess_vec(va_handle h, const double *XP, const double *P, const double *V,
     if (np) HIPCHK(hipMemcpyAsync(p_d, P, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(v_d, V, sizeof(double) * nv, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(hv_d, 0, sizeof(double) * nv, h->stream));      // (the padding between n_var and ld)
-    a.X = x_d; a.pp.Pfull = p_d; a.V = v_d; a.HV = hv_d; a.part = part_d;
-    const hipError_t e = h->rt_hvp.hvp(a, geo.lds_bytes, h->stream);
+    const hipError_t e = hvp_on_device(h, geo, x_d, p_d, v_d, hv_d, part_d, npts, nvec, ld, rf_scale, gauss_newton);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
         return fail(VA_EHIP, "k_hvp launch: %s", hipGetErrorString(e));
     }
     HIPCHK(hipMemcpyAsync(HV, hv_d, sizeof(double) * nv, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    return VA_OK;
+}
+
+// Selected inverse and log-determinant of npts block-tridiagonal arrow matrices given by their blocks (va_selinv.h), on the
+// handle's device and stream, on buffers of its own.  Any handle serves: the blocks are the caller's.
+int va_blocktri_selinv(va_handle h, int32_t npts, int32_t K, int32_t W, int32_t NPe, const double *Dk, const double *Bk,
+                       const double *Pk, const double *Hpp, double *Skk, double *Snk, double *Spk, double *Spp, double *logdet,
+                       int32_t *status)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    if (npts < 1 || K < 1 || W < 1 || NPe < 0) return fail(VA_EINVAL, "bad sizes (npts=%d K=%d W=%d NPe=%d)", npts, K, W, NPe);
+    if (!Dk || (K > 1 && !Bk) || (NPe > 0 && (!Pk || !Hpp)) || !logdet || !status)
+        return fail(VA_EINVAL, "Dk, Bk (K > 1), Pk and Hpp (NPe > 0), logdet and status must not be NULL");
+    SelinvArgs a;
+    if (!plan_selinv(W, K, NPe, npts, a.g)) return fail(VA_EUNSUPPORTED, "va_blocktri_selinv: W=%d NPe=%d: %s", W, NPe, a.g.why);
+    HIPCHK(hipSetDevice(h->device));
+    const size_t ww = (size_t)W * W, pw = (size_t)NPe * W;
+    const size_t nd = npts * K * ww, nb = npts * (K - 1) * ww, np = npts * K * pw, nh = (size_t)npts * NPe * NPe;
+    const size_t nws = (size_t)npts * a.g.ws_doubles;
+    // one allocation: [D | B | P | Hpp | Skk | Snk | Spk | Spp | logdet | workspace | status]
+    const size_t tot = 2 * (nd + nb + np + nh) + npts + nws;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (tot + 1) + sizeof(int) * npts));
+    struct Free { double *q; ~Free() { (void)hipFree(q); } } guard{buf};
+    double *d_d = buf, *b_d = d_d + nd, *p_d = b_d + nb, *h_d = p_d + np, *skk_d = h_d + nh, *snk_d = skk_d + nd,
+           *spk_d = snk_d + nb, *spp_d = spk_d + np, *ld_d = spp_d + nh, *ws_d = ld_d + npts;
+    int *st_d = (int *)(ws_d + nws + 1);
+    HIPCHK(hipMemcpyAsync(d_d, Dk, sizeof(double) * nd, hipMemcpyHostToDevice, h->stream));
+    if (nb) HIPCHK(hipMemcpyAsync(b_d, Bk, sizeof(double) * nb, hipMemcpyHostToDevice, h->stream));
+    if (np) HIPCHK(hipMemcpyAsync(p_d, Pk, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+    if (nh) HIPCHK(hipMemcpyAsync(h_d, Hpp, sizeof(double) * nh, hipMemcpyHostToDevice, h->stream));
+    a.Dk = d_d; a.Bk = b_d; a.Pk = p_d; a.Hpp = h_d;
+    a.Skk = Skk ? skk_d : nullptr; a.Snk = Snk ? snk_d : nullptr; a.Spk = Spk ? spk_d : nullptr; a.Spp = Spp ? spp_d : nullptr;
+    a.logdet = ld_d; a.status = st_d; a.ws = ws_d; a.npts = npts;
+    const hipError_t e = launch_selinv(a, h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
+        return fail(VA_EHIP, "k_selinv launch: %s", hipGetErrorString(e));
+    }
+    if (Skk) HIPCHK(hipMemcpyAsync(Skk, skk_d, sizeof(double) * nd, hipMemcpyDeviceToHost, h->stream));
+    if (Snk && nb) HIPCHK(hipMemcpyAsync(Snk, snk_d, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
+    if (Spk && np) HIPCHK(hipMemcpyAsync(Spk, spk_d, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
+    if (Spp && nh) HIPCHK(hipMemcpyAsync(Spp, spp_d, sizeof(double) * nh, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(logdet, ld_d, sizeof(double) * npts, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(status, st_d, sizeof(int) * npts, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    return VA_OK;
+}
+
+// Laplace approximation at npts points: the coloured directions, k_hvp, k_hblocks, k_selinv and k_laplace_unpack per chunk of
+// points, each point with its own rf_scale (consecutive points of equal rf_scale share a k_hvp launch).  Like va_hess_vec it
+// ignores bounds and leaves the resident paths, seed states and captured graphs alone.
+int va_laplace(va_handle h, const double *XP, const double *P, int32_t npts, int64_t ld, const double *rf_scale,
+               int32_t gauss_newton, int32_t chunk_pts, double *var_x, double *cov_xx, double *cov_px, double *cov_pp,
+               double *logdet, int32_t *status)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    if (!XP || !rf_scale || !var_x || !logdet || !status) return fail(VA_EINVAL, "XP / rf_scale / var_x / logdet / status must not be NULL");
+    if (npts < 1 || chunk_pts < 0) return fail(VA_EINVAL, "npts must be at least 1 and chunk_pts at least 0 (npts=%d chunk_pts=%d)", npts, chunk_pts);
+    TRY(hvp_refusals(h, "va_laplace"));
+    const Dims &hd = h->dv.dm;
+    const int64_t n_var = (int64_t)hd.ND + hd.NPest;
+    if (ld < n_var) return fail(VA_EINVAL, "ld < n_var (%lld < %lld)", (long long)ld, (long long)n_var);
+    if (hd.NPt > 0 && !P) return fail(VA_EINVAL, "P must not be NULL (the model has %d parameter(s))", hd.NPt);
+    HblocksGeo hg;
+    hg.N = hd.N; hg.D = hd.D; hg.hb = hd.disc == DISC_SH ? 2 : 1; hg.NPe = hd.NPest; hg.ld = (long)ld;
+    const int W = hblocks_W(hg), K = hblocks_K(hg), NPe = hd.NPest, nvec = hblocks_nvec(hg);
+    SelinvGeo sg;
+    if (hd.D > SELINV_MAX_W || !plan_selinv(W, K, NPe, npts, sg))
+        return fail(VA_EUNSUPPORTED, "va_laplace: D=%d (blocks of %d time row(s): W=%d) NPest=%d: %s", hd.D, hg.hb, W, NPe,
+                    hd.D > SELINV_MAX_W ? "block wider than 64 (D <= 64, or D <= 32 with SimpsonHermite)" : sg.why);
+    HvpGeo geo;
+    if (!plan_hvp(hd.D, hd.N, hd.disc, hd.NPt, 1, nvec, 0, geo)) return fail(VA_EUNSUPPORTED, "va_laplace: D=%d: %s", hd.D, geo.why);
+    const size_t per = laplace_point_doubles(hg, sg, hd.NPt, geo.ntiles);
+    const long fit = laplace_chunk_points(per, npts);
+    if (chunk_pts > 0 ? (size_t)chunk_pts * per * sizeof(double) > LAPLACE_WORKSPACE_BYTES : fit < 1)
+        return fail(VA_EINVAL, "va_laplace: a chunk of %d point(s) takes %.1f MiB of device workspace (%zu B per point), the limit is %zu MiB",
+                    chunk_pts > 0 ? chunk_pts : 1, (chunk_pts > 0 ? chunk_pts : 1) * (double)per * 8.0 / 1048576.0, per * sizeof(double),
+                    LAPLACE_WORKSPACE_BYTES >> 20);
+    const int C = (int)(chunk_pts > 0 ? (chunk_pts < npts ? chunk_pts : npts) : fit);
+    HIPCHK(hipSetDevice(h->device));
+    const size_t ww = (size_t)W * W, pw = (size_t)NPe * W, ND = (size_t)hd.N * hd.D;
+    const size_t nx = (size_t)C * ld, np = (size_t)C * hd.NPt, nv = (size_t)C * nvec * ld, npart = (size_t)C * nvec * geo.ntiles * (hd.NPt > 0 ? hd.NPt : 1),
+                 nd = C * K * ww, nb = C * (K - 1) * ww, npk = C * K * pw, nh = (size_t)C * NPe * NPe, nws = (size_t)C * sg.ws_doubles,
+                 nvar = C * ND, nxx = C * ND * hd.D, npx = C * NPe * ND;
+    // one allocation: [X | P | V | HV | partial parameter rows | D | B | P_k | Hpp | workspace | Skk | Spk | Spp | logdet |
+    //                  var_x | cov_xx | cov_px | status]
+    const size_t tot = nx + np + 2 * nv + npart + nd + nb + npk + nh + nws + nd + npk + nh + C + nvar + nxx + npx;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (tot + 1) + sizeof(int) * C));
+    struct Free { double *q; ~Free() { (void)hipFree(q); } } guard{buf};
+    double *x_d = buf, *p_d = x_d + nx, *v_d = p_d + np, *hv_d = v_d + nv, *part_d = hv_d + nv, *d_d = part_d + npart, *b_d = d_d + nd,
+           *pk_d = b_d + nb, *h_d = pk_d + npk, *ws_d = h_d + nh, *skk_d = ws_d + nws, *spk_d = skk_d + nd, *spp_d = spk_d + npk,
+           *ld_d = spp_d + nh, *var_d = ld_d + C, *xx_d = var_d + nvar, *px_d = xx_d + nxx;
+    int *st_d = (int *)(px_d + npx + 1);
+    hipError_t e = launch_hcolour(hg, v_d, C, h->stream);                 // (the same directions for every chunk)
+    if (e != hipSuccess) return fail(VA_EHIP, "k_hcolour launch: %s", hipGetErrorString(e));
+    for (int p0 = 0; p0 < npts; p0 += C) {
+        const int n = npts - p0 < C ? npts - p0 : C;
+        HIPCHK(hipMemcpyAsync(x_d, XP + (size_t)p0 * ld, sizeof(double) * n * ld, hipMemcpyHostToDevice, h->stream));
+        if (hd.NPt) HIPCHK(hipMemcpyAsync(p_d, P + (size_t)p0 * hd.NPt, sizeof(double) * n * hd.NPt, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemsetAsync(hv_d, 0, sizeof(double) * (size_t)n * nvec * ld, h->stream));      // (the padding between n_var and ld)
+        for (int q0 = 0; q0 < n;) {                                       // runs of one rf_scale
+            int q1 = q0 + 1;
+            while (q1 < n && rf_scale[p0 + q1] == rf_scale[p0 + q0]) ++q1;
+            e = hvp_on_device(h, geo, x_d + (size_t)q0 * ld, p_d + (size_t)q0 * hd.NPt, v_d, hv_d + (size_t)q0 * nvec * ld,
+                              part_d + (size_t)q0 * nvec * geo.ntiles * hd.NPt, q1 - q0, nvec, ld, rf_scale[p0 + q0], gauss_newton);
+            if (e != hipSuccess) {
+                (void)hipStreamSynchronize(h->stream);
+                return fail(VA_EHIP, "k_hvp launch: %s", hipGetErrorString(e));
+            }
+            q0 = q1;
+        }
+        HblocksArgs ba;
+        ba.h = hg; ba.HV = hv_d; ba.Dk = d_d; ba.Bk = b_d; ba.Pk = pk_d; ba.Hpp = h_d; ba.npts = n;
+        SelinvArgs sa;
+        sa.g = sg; sa.g.grid = n;
+        sa.Dk = d_d; sa.Bk = b_d; sa.Pk = pk_d; sa.Hpp = h_d; sa.Skk = skk_d; sa.Snk = nullptr; sa.Spk = spk_d; sa.Spp = spp_d;
+        sa.logdet = ld_d; sa.status = st_d; sa.ws = ws_d; sa.npts = n;
+        UnpackArgs ua;
+        ua.h = hg; ua.Skk = skk_d; ua.Spk = spk_d; ua.var_x = var_d; ua.cov_xx = cov_xx ? xx_d : nullptr; ua.cov_px = cov_px ? px_d : nullptr;
+        ua.npts = n;
+        if ((e = launch_hblocks(ba, h->stream)) != hipSuccess || (e = launch_selinv(sa, h->stream)) != hipSuccess
+            || (e = launch_laplace_unpack(ua, h->stream)) != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);
+            return fail(VA_EHIP, "k_hblocks / k_selinv / k_laplace_unpack launch: %s", hipGetErrorString(e));
+        }
+        HIPCHK(hipMemcpyAsync(var_x + (size_t)p0 * ND, var_d, sizeof(double) * n * ND, hipMemcpyDeviceToHost, h->stream));
+        if (cov_xx) HIPCHK(hipMemcpyAsync(cov_xx + (size_t)p0 * ND * hd.D, xx_d, sizeof(double) * n * ND * hd.D, hipMemcpyDeviceToHost, h->stream));
+        if (cov_px && NPe) HIPCHK(hipMemcpyAsync(cov_px + (size_t)p0 * NPe * ND, px_d, sizeof(double) * n * NPe * ND, hipMemcpyDeviceToHost, h->stream));
+        if (cov_pp && NPe) HIPCHK(hipMemcpyAsync(cov_pp + (size_t)p0 * NPe * NPe, spp_d, sizeof(double) * n * NPe * NPe, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(logdet + p0, ld_d, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(status + p0, st_d, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
+    }
     HIPCHK(hipGetLastError());
     return VA_OK;
 }

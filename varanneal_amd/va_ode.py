@@ -513,6 +513,49 @@ class Annealer(LadderAnnealer):
         out = np.array(out)
         return out if self._batched else out[0]
 
+    def laplace(self, beta=None, seeds=None, gauss_newton=False, full=False):
+        """Laplace approximation at the stored minimisers of every selected (seed, rung), each with its own rung's RF, in
+        ONE device call (va_laplace; csrc/va_selinv.h): the Hessian from coloured Hessian-vector products, its
+        block-tridiagonal Cholesky factor with the parameter border carried along, and the inverse on the factor's own
+        sparsity pattern.  Returns a dict:
+          state_var   (..., N, D)          marginal variance of every state, observed or not
+          param_cov   (..., NPest, NPest)  what param_covariance computes on the host
+          logdet      (...)                log det H: with the action value, the evidence of a minimiser
+          status      (...)                0, or where the Hessian stopped being positive definite: k + 1 in block k of the
+                                           path (hb = 1 time row per block, 2 with Simpson-Hermite), -1 in the parameters'
+                                           Schur complement; the other entries of such a point are NaN.  Never raises for it.
+        and with full=True also
+          state_cov        (..., N, D, D)        the same-time covariance blocks
+          state_param_cov  (..., NPest, N, D)    covariance of parameters and states.
+        Leading axes as predict(): (nbeta_sel,), or (B_sel, nbeta_sel) for a batch.  beta / seeds: an int or a sequence;
+        None = all.  It is the inverse Hessian of the action AS THE PACKAGE NORMALISES IT (measurement term / (L N_data),
+        model term / (D (N - 1))): for a negative log-likelihood A' = c A the covariances are these divided by c, and
+        logdet grows by n_var log c.  States wider than 64 (32 with Simpson-Hermite) or more than 32 estimated parameters:
+        NotImplementedError; param_covariance's host route remains."""
+        if self._pb is None or not getattr(self, "initalized", False):
+            raise ValueError("second derivatives are taken at the minimisers: call anneal() first")
+        if self._tdp:
+            raise NotImplementedError("laplace: time-dependent parameters are not carried")
+        sb, kb = self._select(beta, seeds)
+        N, D, NPe, NX = self.N_model, self.D, self.NPest, self._NX
+        rows = self._mp[sb][:, kb].reshape(len(sb) * len(kb), -1)                # (points, NX + NP)
+        P = np.ascontiguousarray(rows[:, NX:])
+        XP = np.concatenate([rows[:, :NX], P[:, self.Pidx]], axis=1)
+        rf = np.tile(np.asarray(self._rf_scale, dtype=np.float64)[kb], len(sb))
+        r = self._pb.laplace(XP, rf, P=P, gauss_newton=gauss_newton, full=full)
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        out = dict(state_var=r["var_x"].reshape(lead + (N, D)), param_cov=r["cov_pp"].reshape(lead + (NPe, NPe)),
+                   logdet=r["logdet"].reshape(lead), status=r["status"].reshape(lead))
+        if full:
+            out["state_cov"] = r["cov_xx"].reshape(lead + (N, D, D))
+            out["state_param_cov"] = r["cov_px"].reshape(lead + (NPe, N, D))
+        return out
+
+    def state_stderr(self, beta=-1, seeds=None, gauss_newton=False):
+        """One standard deviation of every estimated state at the selected rung(s): sqrt(laplace()['state_var']), shape
+        (nbeta_sel, N, D) or (B_sel, nbeta_sel, N, D); NaN where the Hessian is not positive definite."""
+        return np.sqrt(self.laplace(beta=beta, seeds=seeds, gauss_newton=gauss_newton)["state_var"])
+
     def me_gaussian(self, X):
         """Measurement error of a path (va_ode.py:138-158); X may omit the parameters."""
         X = np.asarray(X, dtype=np.float64)
