@@ -5,9 +5,11 @@ Counterpart of the reference's examples/Lorenz96_D20/Lorenz96_anneal.py (SURVEY.
 edits are the import (varanneal_amd instead of varanneal), an explicit RNG seed, and
 the data file location.  Optional: --seeds B runs B random initial paths as one batch;
 --predict N holds the last N observations back from the fit, integrates the model N steps on
-from every rung's estimate (Annealer.predict) and prints the forecast's RMS error per rung.
+from every rung's estimate (Annealer.predict) and prints the forecast's RMS error per rung;
+--spread N holds them back as well and prints the last rung's forecast with its +- 2 sigma band
+(Annealer.predict_spread) and the share of held-back observed values inside it at a few lead times.
 
-    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40]
+    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40] [--spread 40]
 """
 import argparse
 import os
@@ -34,6 +36,9 @@ def main():
     ap.add_argument("--out", default=".")
     ap.add_argument("--predict", type=int, default=0, metavar="N",
                     help="hold the last N observations back and report the forecast error per rung")
+    ap.add_argument("--spread", type=int, default=0, metavar="N",
+                    help="hold the last N observations back and print the last rung's forecast +- 2 sigma (linearised spread "
+                         "under the Laplace posterior: Annealer.predict_spread) and the share of them inside the band")
     ap.add_argument("--errorbars", action="store_true",
                     help="print the final k +- sigma per seed (Laplace approximation: Annealer.param_covariance)")
     ap.add_argument("--statebars", action="store_true",
@@ -58,10 +63,13 @@ def main():
     N_data = len(times_data)
     data = data[:, 1:][:, Lidx]
     held_back = None
-    if args.predict > 0:
+    if args.predict > 0 and args.spread > 0 and args.predict != args.spread:
+        ap.error("--predict and --spread hold the same rows back: give them the same N")
+    hold = max(args.predict, args.spread)
+    if hold > 0:
         # fit what comes before the last N rows (Simpson-Hermite needs an odd number of them); the last fitted row is
         # row 0 of what the forecast is compared with
-        n_fit = N_data - args.predict
+        n_fit = N_data - hold
         first = 1 if (args.disc == "SimpsonHermite" and n_fit % 2 == 0) else 0
         held_back = data[n_fit - 1:]
         data, times_data, N_data = data[first:n_fit], times_data[first:n_fit], n_fit - first
@@ -90,11 +98,34 @@ def main():
     print("\nHIP annealing completed in %f s." % (time.time() - tstart))
     print("estimated forcing k (true value 8.17): %s" % np.ravel(anneal1.P))
 
-    if held_back is not None:
+    if args.predict > 0:
         err = anneal1.prediction_error(held_back)          # (nbeta,), or (seeds, nbeta)
         print("\nforecast of %d steps from every rung's estimate: RMS error on the measured components" % args.predict)
         for k, beta in enumerate(beta_array):
             print("beta = %3d   %s" % (beta, np.array2string(np.atleast_1d(err[..., k]), precision=4)))
+
+    if args.spread > 0:
+        # the model forecast's linearised spread: no observation noise in it, so the band is widened by the measurement
+        # error (RM = 1 / sigma^2) before the held-back values are counted.  Gauss-Newton where the exact Hessian is not
+        # positive definite (status != 0)
+        sp = anneal1.predict_spread(args.spread, beta=-1)
+        if np.any(sp["status"] != 0):
+            print("\n(the exact Hessian is not positive definite at %d of %d seeds: Gauss-Newton part)"
+                  % (int(np.sum(sp["status"] != 0)), sp["status"].size))
+            sp = anneal1.predict_spread(args.spread, beta=-1, gauss_newton=True)
+        # predict_spread's covariance is that of the action as the package normalises it; the negative log-likelihood of
+        # Gaussian measurement noise is A' = c A with c = L N_data / 2 (RM = 1 / sigma^2), so variances are divided by c
+        c_nll = 0.5 * len(Lidx) * N_model
+        mean, std = sp["mean"].reshape(-1, args.spread + 1, D), sp["std"].reshape(-1, args.spread + 1, D) / np.sqrt(c_nll)
+        leads = sorted(set(int(round(f * args.spread)) for f in (0.1, 0.25, 0.5, 0.75, 1.0)) - {0})
+        print("\nforecast of the last rung, x_0 +- 2 sigma (model spread, sigma^2 / (L N / 2)), and the share of the %d held-back observed values within "
+              "2 sqrt(sigma^2 + 1/RM)" % len(Lidx))
+        for b in range(mean.shape[0]):
+            for n in leads:
+                band = 2.0 * np.sqrt(std[b, n, Lidx] ** 2 + 1.0 / RM)
+                inside = np.mean(np.abs(held_back[n] - mean[b, n, Lidx]) <= band)
+                print("seed %d   lead %3d steps   x_0 = %8.4f +- %.4f   inside the band: %3.0f %%"
+                      % (b, n, mean[b, n, 0], 2.0 * std[b, n, 0], 100.0 * inside))
 
     if args.errorbars:
         # inverse Hessian of the action as the package normalises it, at the last rung's minimisers; at large RF the

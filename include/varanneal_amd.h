@@ -259,6 +259,26 @@ int va_laplace(va_handle h, const double *XP, const double *P, int32_t npts, int
                int32_t gauss_newton, int32_t chunk_pts, double *var_x, double *cov_xx, double *cov_px, double *cov_pp,
                double *logdet, int32_t *status);
 
+/* Forecast spread: va_predict's trajectories and, with each, the tangent-linear model of the discrete RK4 map along nvec
+ * directions (csrc/va_predict_tlm.h: every stage's k' = J(x_stage) v_stage + (df/dp) v_p, the exact derivative of the
+ * integrator, not of the differential equation), and their sums over directions.  With the directions of a trajectory
+ * the columns of a square root S of the covariance Sigma_0 = S S^T of (x0, p_est), var and cov are the linearised forecast
+ * covariance M_n Sigma_0 M_n^T at every output row.
+ *   x0, p, T, t0, n_steps, substeps, every, stim as in va_predict (the stimulus is known: it has no tangent)
+ *   V0 [T*nvec*(D+NPest)] HOST: per direction the state part, then the estimated parameters' in Pidx order (constant)
+ *   out [T*n_out*D] the nominal trajectory, row 0 is x0
+ *   dX [T*nvec*n_out*D] the tangents' state parts, row 0 is V0's state part; var [T*n_out*D] = sum over directions of
+ *        dX^2; cov [T*n_out*D*D] = sum over directions of dX_i dX_j at equal times; each may be NULL: not wanted.  The sums
+ *        run in direction order, products and additions rounded one by one: the same bits on every call.
+ * All arrays HOST.  The tangents live in a device workspace chunked over trajectories (a chunk under 1 GiB).  The handle's
+ * resident paths, seed states and captured graphs are left alone.
+ * VA_EINVAL: what va_predict rejects; nvec < 1.
+ * VA_EUNSUPPORTED (reason in va_last_error): network handles; D > 1024; generated models without a flat form (more than
+ * 128 parameters); modules with a split linear part; one trajectory's tangents past the workspace limit. */
+int va_predict_tangent(va_handle h, const double *x0, const double *p, const double *V0, int32_t T, int32_t nvec, double t0,
+                       int32_t n_steps, int32_t substeps, int32_t every, const double *stim, double *out, double *dX,
+                       double *var, double *cov);
+
 /* Measurement hook for bench.py: `iters` complete S1 evaluations (the same launch va_action_grad
  * makes: A, me, fe and the full gradient are formed every time) on the resident paths (those of
  * the last va_action_grad / va_anneal call), bracketed by HIP events on the handle's stream;

@@ -205,6 +205,8 @@ def lib():
                             C.POINTER(LbfgsOpts), c_dp, c_dp, c_ip, c_ip, c_lp, c_dp]
     L.va_get_minpath.argtypes = [h, C.c_int32, C.c_int32, c_dp]
     L.va_predict.argtypes = [h, c_dp, c_dp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp]
+    L.va_predict_tangent.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32] + [c_dp] * 5
+    L.va_predict_tangent.restype = C.c_int
     L.va_hess_vec.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, c_dp]
     L.va_hess_vec.restype = C.c_int
     L.va_blocktri_selinv.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [c_dp] * 9 + [c_ip]
@@ -241,7 +243,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -471,6 +473,49 @@ class Problem(object):
         check(self._L.va_predict(self._h, x0.ctypes.data_as(c_dp), p.ctypes.data_as(c_dp), T, float(t0), n_steps, substeps,
                                  every, st.ctypes.data_as(c_dp) if st is not None else None, out.ctypes.data_as(c_dp)))
         return out
+
+    def predict_tangent(self, x0, p, V0, n_steps, t0=0.0, substeps=1, every=1, stim=None, want=("dx", "var")):
+        """predict() and, along the nvec directions V0 (T, nvec, D + NPest) of every trajectory ([state part | estimated
+        parameters' part], or (nvec, D + NPest) for one trajectory), the tangent-linear model of the discrete RK4 map on the
+        device (va_predict_tangent; csrc/va_predict_tlm.h).  Returns a dict: out (T, n_out, D), the nominal trajectories,
+        and of want: dx (T, nvec, n_out, D), the tangents' state parts (row 0 is V0's); var (T, n_out, D), their squares
+        summed over directions; cov (T, n_out, D, D), the same-time products summed over directions.  With V0 a square
+        root of the covariance of (x0, p_est), var and cov are the linearised forecast covariance."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("predict_tangent: a network handle has no differential equation to integrate")
+        bad = set(want) - {"dx", "var", "cov"}
+        if bad:
+            raise ValueError("predict_tangent: want holds 'dx', 'var', 'cov', not %s" % sorted(bad))
+        D, NP, nw = self.desc.D, self.desc.NP, self.desc.D + self.NPest
+        x0 = _f64(x0).reshape(-1, D)
+        T = x0.shape[0]
+        p = _f64(p).reshape(-1, NP) if NP else np.zeros((T, 0))
+        if p.shape[0] == 1 and T > 1:
+            p = np.ascontiguousarray(np.broadcast_to(p, (T, NP)))
+        if p.shape[0] != T:
+            raise ValueError("predict_tangent: %d states but %d parameter vectors" % (T, p.shape[0]))
+        V0 = _f64(V0)
+        if V0.size == 0:
+            raise ValueError("predict_tangent: at least one direction (nvec = 0)")
+        if V0.shape[-1:] != (nw,) or V0.size % (T * nw):
+            raise ValueError("predict_tangent: V0 must have shape (%d, nvec, D + NPest = %d), got %s" % (T, nw, V0.shape))
+        V0 = V0.reshape(T, -1, nw)
+        nvec = V0.shape[1]
+        n_steps, substeps, every = int(n_steps), int(substeps), int(every)
+        st = None
+        if stim is not None:
+            st = _f64(stim).reshape(max(n_steps, 0) + 1, -1)
+            if st.shape[1] != self.desc.n_stim and self.desc.n_stim:
+                raise ValueError("predict_tangent: the stimulus must have %d rows of %d column(s)" % (n_steps + 1, self.desc.n_stim))
+        n_out = n_steps // every + 1 if every >= 1 and n_steps >= 1 else 1
+        r = dict(out=np.empty((T, n_out, D)))
+        for name, shape in (("dx", (T, nvec, n_out, D)), ("var", (T, n_out, D)), ("cov", (T, n_out, D, D))):
+            if name in want:
+                r[name] = np.empty(shape)
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
+        check(self._L.va_predict_tangent(self._h, ptr(x0), ptr(p), ptr(V0), T, nvec, float(t0), n_steps, substeps, every, ptr(st),
+                                         ptr(r["out"]), ptr(r.get("dx")), ptr(r.get("var")), ptr(r.get("cov"))))
+        return r
 
     def hess_vec(self, XP, V, rf_scale, P=None, gauss_newton=False, tile_rows=0):
         """Hessian-vector products of the action on the device (va_hess_vec): XP (npts, n_var) points, V (npts, nvec, n_var)

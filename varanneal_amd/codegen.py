@@ -502,7 +502,7 @@ def generate_header(exprs, syms, D, NP, nstim, name="user", col=None, ghost=None
             _switch_flat(out, exprs, syms, D, NP, pr, sv)
     out.append("};")
     if NP <= MAX_NP:
-        out.append("#define VA_USER_FLAT 1       // the flat struct is complete: the module also carries the predictor (va_predict.h) and the Hessian-vector kernel (va_hvp.h)")
+        out.append("#define VA_USER_FLAT 1       // the flat struct is complete: the module also carries the predictor (va_predict.h), its tangent-linear model (va_predict_tlm.h) and the Hessian-vector kernel (va_hvp.h)")
     if col is not None:
         out.append("// the same model in column form (codegen.column_form): %s"
                    % ("translation-invariant stencil, offsets %s" % col["offsets"] if col["uniform"] else "dense, switch on the column"))
@@ -993,7 +993,7 @@ BUILD_TAG = "sched=iterative-maxocc"      # part of every module's cache key: a 
 def _core_fingerprint():
     h = hashlib.sha1(BUILD_TAG.encode())
     for fn in ("va_core.h", "va_device.h", "va_eval_flat.h", "va_eval3.h", "va_eval4.h", "va_epilogue.h", "va_tile2.h", "va_tile3.h",
-               "va_tile4.h", "va_tile5.h", "va_eval5.h", "va_persist.h", "va_persist_geo.h", "va_measure.h", "va_predict.h", "va_predict_geo.h",
+               "va_tile4.h", "va_tile5.h", "va_eval5.h", "va_persist.h", "va_persist_geo.h", "va_measure.h", "va_predict.h", "va_predict_geo.h", "va_predict_tlm.h", "va_predict_tlm_geo.h",
                "va_hvp.h", "va_hvp_geo.h",
                "va_user_rhs.hip"):
         with open(os.path.join(CSRC, fn), "rb") as fh:

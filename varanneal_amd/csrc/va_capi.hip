@@ -38,6 +38,7 @@
 #include "va_eval_flat.h"
 #include "va_persist.h"
 #include "va_predict.h"
+#include "va_predict_tlm.h"
 #include "va_hvp.h"
 #include "va_selinv.h"
 
@@ -965,7 +966,7 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
     typedef int (*hvp_fn)(HvpTable *, int);
     if (hvp_fn hv = (hvp_fn)dlsym(u.dl, "va_user_hvp_table")) {
         const int hb = hv(&u.hvp, (int)sizeof(HvpTable));
-        if (hb != (int)sizeof(HvpTable) || u.hvp.hvp_bytes != (int)sizeof(HvpArgs)) {
+        if (hb != (int)sizeof(HvpTable) || u.hvp.hvp_bytes != (int)sizeof(HvpArgs) || u.hvp.tlm_bytes != (int)sizeof(PredictTlmArgs)) {
             dlclose(u.dl);
             return fail(VA_EINVAL, "%s was built against different headers (HvpTable %d vs %zu bytes): rebuild it", path, hb, sizeof(HvpTable));
         }
@@ -1217,6 +1218,82 @@ int va_predict(va_handle h, const double *x0, const double *p, int32_t T, double
     }
     HIPCHK(hipMemcpyAsync(out, out_d, sizeof(double) * no, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    return VA_OK;
+}
+
+// Forecast spread: the nominal trajectories of va_predict and, along nvec directions each, the tangent-linear model of the
+// discrete RK4 map (va_predict_tlm.h); the tangents stay in a device workspace [T][nvec][n_out][D], which k_spread reduces
+// to variances and same-time covariance blocks.  Chunked over trajectories: the buffers of a chunk stay under 1 GiB.  Works
+// on buffers of its own, like va_predict.
+int va_predict_tangent(va_handle h, const double *x0, const double *p, const double *V0, int32_t T, int32_t nvec, double t0,
+                       int32_t n_steps, int32_t substeps, int32_t every, const double *stim, double *out, double *dX, double *var,
+                       double *cov)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    if (!x0 || !p || !V0 || !out) return fail(VA_EINVAL, "x0 / p / V0 / out must not be NULL");
+    if (T < 1 || n_steps < 1 || substeps < 1 || every < 1)
+        return fail(VA_EINVAL, "T, n_steps, substeps and every must be at least 1 (T=%d n_steps=%d substeps=%d every=%d)", T, n_steps, substeps, every);
+    if (nvec < 1) return fail(VA_EINVAL, "nvec must be at least 1 (nvec=%d)", nvec);
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "a network handle has no differential equation to integrate");
+    const Dims &dm = h->dv.dm;
+    const int nstim = h->dv.pp.nstim;
+    if (nstim > 0 && !stim) return fail(VA_EINVAL, "the model takes a stimulus of %d column(s): pass its %d rows from t0 on", nstim, n_steps + 1);
+    if (nstim == 0 && stim) return fail(VA_EINVAL, "the model takes no stimulus, but one was passed");
+    if (dm.lin) return fail(VA_EUNSUPPORTED, "va_predict_tangent: the module's dense linear part was split off (LINEAR): build it with linear=False");
+    if (!h->rt.predict || !h->rt_hvp.predict_tlm)
+        return fail(VA_EUNSUPPORTED, "va_predict_tangent: the model has no flat form f(x, i, p) to differentiate (more than %d parameters: "
+                                     "its module carries the column-parameter form only)", RHS_BIG_NP);
+    if ((int64_t)n_steps * substeps > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_steps x substeps does not fit 32-bit indexing");
+    PredictTlmArgs a;
+    a.T = T; a.D = dm.D; a.NP = dm.NPt; a.NPest = dm.NPest; a.nvec = nvec; a.nstim = nstim; a.n_steps = n_steps; a.substeps = substeps;
+    a.every = every; a.n_out = n_steps / every + 1; a.t0 = t0; a.dt = dm.dt; a.Pidx = h->dv.pp.Pidx;
+    const bool reduce = var || cov;
+    const size_t per = predict_tlm_traj_doubles(a.D, a.NP, a.NPest, nvec, a.n_out, cov != nullptr);
+    const long C = predict_tlm_chunk_trajs(per, T);
+    if (C < 1)
+        return fail(VA_EUNSUPPORTED, "va_predict_tangent: one trajectory with %d direction(s) and %d output row(s) takes %.1f MiB of device "
+                                     "workspace, the limit is %zu MiB: fewer directions, or a larger `every`", nvec, a.n_out,
+                    (double)per * 8.0 / 1048576.0, PREDICT_TLM_WORKSPACE_BYTES >> 20);
+    if (!plan_predict_tlm(a.D, C, nvec, a.NP, nstim, a.geo)) return fail(VA_EUNSUPPORTED, "va_predict_tangent: D=%d nvec=%d: %s", a.D, nvec, a.geo.why);
+    HIPCHK(hipSetDevice(h->device));
+    // one allocation: [stim | x0 | p | V0 | out | dX | var | cov], all but the stimulus for one chunk of C trajectories
+    const size_t nw = (size_t)a.D + a.NPest, row = (size_t)a.n_out * a.D;
+    const size_t ns = (size_t)(n_steps + 1) * nstim, nx = (size_t)C * a.D, np = (size_t)C * a.NP, nv0 = (size_t)C * nvec * nw, no = C * row,
+                 ndx = (dX || reduce) ? C * nvec * row : 0, nvar = var ? C * row : 0, ncov = cov ? C * row * a.D : 0;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (ns + nx + np + nv0 + no + ndx + nvar + ncov + 1)));
+    struct Free { double *q; ~Free() { (void)hipFree(q); } } guard{buf};
+    double *st_d = buf, *x0_d = st_d + ns, *p_d = x0_d + nx, *v0_d = p_d + np, *out_d = v0_d + nv0, *dx_d = out_d + no, *var_d = dx_d + ndx,
+           *cov_d = var_d + nvar;
+    if (ns) HIPCHK(hipMemcpyAsync(st_d, stim, sizeof(double) * ns, hipMemcpyHostToDevice, h->stream));
+    for (long t1 = 0; t1 < T; t1 += C) {
+        const long n = T - t1 < C ? T - t1 : C;
+        HIPCHK(hipMemcpyAsync(x0_d, x0 + (size_t)t1 * a.D, sizeof(double) * n * a.D, hipMemcpyHostToDevice, h->stream));
+        if (a.NP) HIPCHK(hipMemcpyAsync(p_d, p + (size_t)t1 * a.NP, sizeof(double) * n * a.NP, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(v0_d, V0 + (size_t)t1 * nvec * nw, sizeof(double) * n * nvec * nw, hipMemcpyHostToDevice, h->stream));
+        a.T = (int)n;
+        if (!plan_predict_tlm(a.D, n, nvec, a.NP, nstim, a.geo)) {      // (the last chunk: the same plan on fewer workgroups)
+            (void)hipStreamSynchronize(h->stream);
+            return fail(VA_EUNSUPPORTED, "va_predict_tangent: D=%d nvec=%d: %s", a.D, nvec, a.geo.why);
+        }
+        a.x0 = x0_d; a.p = p_d; a.V0 = v0_d; a.stim = ns ? st_d : nullptr; a.out = out_d; a.dX = ndx ? dx_d : nullptr;
+        hipError_t e = h->rt_hvp.predict_tlm(a, h->stream);
+        if (e == hipSuccess && reduce) {
+            SpreadArgs sa;
+            sa.dX = dx_d; sa.var = var ? var_d : nullptr; sa.cov = cov ? cov_d : nullptr; sa.T = (int)n; sa.nvec = nvec; sa.n_out = a.n_out; sa.D = a.D;
+            e = launch_spread(sa, h->stream);
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
+            return fail(VA_EHIP, "k_predict_tlm / k_spread launch: %s", hipGetErrorString(e));
+        }
+        HIPCHK(hipMemcpyAsync(out + (size_t)t1 * row, out_d, sizeof(double) * n * row, hipMemcpyDeviceToHost, h->stream));
+        if (dX) HIPCHK(hipMemcpyAsync(dX + (size_t)t1 * nvec * row, dx_d, sizeof(double) * n * nvec * row, hipMemcpyDeviceToHost, h->stream));
+        if (var) HIPCHK(hipMemcpyAsync(var + (size_t)t1 * row, var_d, sizeof(double) * n * row, hipMemcpyDeviceToHost, h->stream));
+        if (cov) HIPCHK(hipMemcpyAsync(cov + (size_t)t1 * row * a.D, cov_d, sizeof(double) * n * row * a.D, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
+    }
     HIPCHK(hipGetLastError());
     return VA_OK;
 }

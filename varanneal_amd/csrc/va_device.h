@@ -133,12 +133,16 @@ struct RhsTable {
     hipError_t (*predict)(const PredictArgs &, hipStream_t);      // the RK4 predictor (va_predict.h), or NULL
 };
 void builtin_rhs_table(RhsTable &t);
-// The launcher slot of the Hessian-vector kernel (va_hvp.h).  A table of its own beside RhsTable, whose layout modules and
-// their checks already agree on: the built-in fills one in va_kernels.hip (builtin_hvp_table), a generated module through
-// a second entry point, va_user_hvp_table (va_user_rhs.hip); a module without that entry point has no such kernel.
+// The launcher slots of the kernels that call the right-hand side's derivatives along a direction (RHS::jvp and beyond): the
+// Hessian-vector kernel (va_hvp.h) and the tangent-linear predictor (va_predict_tlm.h), the predictor's entry beside
+// `predict`.  A table of its own beside RhsTable, whose layout modules and their checks already agree on: the built-in
+// fills one in va_kernels.hip (builtin_hvp_table), a generated module through a second entry point, va_user_hvp_table
+// (va_user_rhs.hip); a module without that entry point has no such kernels.
+struct PredictTlmArgs;
 struct HvpTable {
-    int bytes, hvp_bytes;                      // sizeof(HvpTable), sizeof(HvpArgs)
+    int bytes, hvp_bytes, tlm_bytes;           // sizeof(HvpTable), sizeof(HvpArgs), sizeof(PredictTlmArgs)
     hipError_t (*hvp)(const HvpArgs &, size_t lds_bytes, hipStream_t);      // or NULL
+    hipError_t (*predict_tlm)(const PredictTlmArgs &, hipStream_t);         // or NULL
 };
 void builtin_hvp_table(HvpTable &t);
 

@@ -26,6 +26,7 @@
 #include "va_tile5.h"
 #include "va_persist.h"
 #include "va_predict.h"
+#include "va_predict_tlm.h"
 #include "va_hvp.h"
 
 namespace va {
@@ -111,8 +112,11 @@ void builtin_rhs_table(RhsTable &t)
     t = RhsTable{(int)sizeof(RhsTable), (int)sizeof(Dev), (int)sizeof(SeedState), (int)sizeof(PredictArgs), RhsL96::NP, 0, 0,
                  eval_builtin, nullptr, seed_op<RhsL96>, launch_predict<RhsL96, 0>};
 }
-// Hessian-vector products (va_hvp.h)
-void builtin_hvp_table(HvpTable &t) { t = HvpTable{(int)sizeof(HvpTable), (int)sizeof(HvpArgs), launch_hvp<RhsL96>}; }
+// Hessian-vector products (va_hvp.h) and the tangent-linear predictor (va_predict_tlm.h)
+void builtin_hvp_table(HvpTable &t)
+{
+    t = HvpTable{(int)sizeof(HvpTable), (int)sizeof(HvpArgs), (int)sizeof(PredictTlmArgs), launch_hvp<RhsL96>, launch_predict_tlm<RhsL96, 0>};
+}
 
 // ------------------------------------------------------------------ K2: tails as kernels of their own
 // (the network action, whose evaluation is several kernels, and grids too large to fold the tail

@@ -556,6 +556,62 @@ class Annealer(LadderAnnealer):
         (nbeta_sel, N, D) or (B_sel, nbeta_sel, N, D); NaN where the Hessian is not positive definite."""
         return np.sqrt(self.laplace(beta=beta, seeds=seeds, gauss_newton=gauss_newton)["state_var"])
 
+    def predict_spread(self, n_steps, beta=None, seeds=None, substeps=1, every=1, stim=None, gauss_newton=False, full=False):
+        """The forecast of predict() with its error bar: the LINEARISED spread of the model forecast under the Laplace
+        posterior of every selected (seed, rung).  One laplace(full=True) call gives the joint covariance Sigma_0 of the
+        last fitted state and the estimated parameters (the last time row's blocks of state_cov and state_param_cov, and
+        param_cov); the columns of its Cholesky factor (host; at most 96 x 96) are carried along the forecast by the
+        tangent-linear model of the RK4 integrator, all selected points in one device call (csrc/va_predict_tlm.h), and
+        summed: the covariance at output row n is M_n Sigma_0 M_n^T, M_n the derivative of the forecast with respect to
+        (x_{N-1}, p_est).  Returns a dict:
+          mean    (..., n_out, D)      predict()'s output
+          std     (..., n_out, D)      one standard deviation of every forecast state; row 0 is state_stderr()'s last row
+          status  (...)                laplace()'s status, or -2 where Sigma_0 has no Cholesky factor; std (and cov) of such
+                                       a point are NaN, its mean is the forecast as usual.  Never raises for it.
+        and with full=True also
+          cov     (..., n_out, D, D)   the same-time covariance blocks.
+        Arguments and leading axes as predict(); gauss_newton as laplace().  What this is and is not: a linearisation, valid
+        while the spread is small against the attractor (tangents of a chaotic model grow without bound; the true spread
+        saturates); the covariance of the action AS THE PACKAGE NORMALISES IT (see laplace(): for a negative
+        log-likelihood A' = c A divide variances by c); the spread of the MODEL forecast only -- no observation noise is
+        added, so held-back data scatter around the band by their own error as well.  Refusals as laplace(): before
+        anneal() ValueError; time-dependent parameters, states wider than 64 (32 with Simpson-Hermite) or more than 32
+        estimated parameters NotImplementedError."""
+        lap = self.laplace(beta=beta, seeds=seeds, gauss_newton=gauss_newton, full=True)
+        sb, kb = self._select(beta, seeds)
+        N, D, NP, NPe, NX = self.N_model, self.D, self.NP, self.NPest, self._NX
+        npts, nw = len(sb) * len(kb), D + NPe
+        status = np.array(lap["status"], dtype=np.int32).reshape(npts)
+        Sxx = lap["state_cov"].reshape(npts, N, D, D)[:, N - 1]
+        Spx = lap["state_param_cov"].reshape(npts, NPe, N, D)[:, :, N - 1]
+        Spp = lap["param_cov"].reshape(npts, NPe, NPe)
+        V0 = np.zeros((npts, nw, nw))                                    # direction c of point j: column c of the factor
+        for j in range(npts):
+            if status[j] != 0:
+                continue
+            S0 = np.empty((nw, nw))
+            S0[:D, :D], S0[D:, :D], S0[:D, D:], S0[D:, D:] = Sxx[j], Spx[j], Spx[j].T, Spp[j]
+            try:
+                if not np.all(np.isfinite(S0)):
+                    raise np.linalg.LinAlgError("not finite")
+                V0[j] = np.linalg.cholesky(S0).T
+            except np.linalg.LinAlgError:
+                status[j] = -2
+        rows = self._mp[sb][:, kb].reshape(npts, -1)
+        r = self._pb.predict_tangent(rows[:, (N - 1) * D:N * D], rows[:, NX:], V0, n_steps, t0=float(self.t_model[-1]),
+                                     substeps=substeps, every=every, stim=stim, want=("var", "cov") if full else ("var",))
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        n_out = r["out"].shape[1]
+        bad = status != 0
+        std = np.sqrt(r["var"])
+        std[bad] = np.nan
+        out = dict(mean=r["out"].reshape(lead + (n_out, D)), std=std.reshape(lead + (n_out, D)), status=status.reshape(lead))
+        if full:
+            cov = np.array(r["cov"])
+            cov[bad] = np.nan
+            out["cov"] = cov.reshape(lead + (n_out, D, D))
+        return out
+
     def me_gaussian(self, X):
         """Measurement error of a path (va_ode.py:138-158); X may omit the parameters."""
         X = np.asarray(X, dtype=np.float64)
