@@ -44,6 +44,9 @@ def main():
     ap.add_argument("--statebars", action="store_true",
                     help="print the RMS sigma of the observed and of the unobserved columns at the last rung, and log det H, "
                          "per seed (Laplace approximation on the device: Annealer.laplace)")
+    ap.add_argument("--sample", type=int, default=0, metavar="N",
+                    help="sample exp(-A) at the last rung, N states per seed (Hamiltonian Monte Carlo on the device: "
+                         "Annealer.sample), and print k +- std from the chains beside the Laplace sigma, with the acceptance rate")
     args = ap.parse_args()
 
     D = 20
@@ -152,6 +155,20 @@ def main():
         for b in range(var.shape[0]):
             print("seed %d   RMS sigma: observed %.3e  unobserved %.3e   log det H = %.4f"
                   % (b, np.sqrt(np.mean(var[b][:, Lidx])), np.sqrt(np.mean(var[b][:, unobserved])), np.ravel(lap["logdet"])[b]))
+
+    if args.sample > 0:
+        # exp(-A) at the last rung sampled by Hamiltonian Monte Carlo on the device, the Laplace variances as masses, the
+        # step sizes adapted over a warm-up as long as the run; beside it the Laplace sigma of the same normalisation
+        s = anneal1.sample(args.sample, beta=-1, warmup=args.sample, seed=args.rng)
+        if s["mass_note"][0]:
+            print("\n(%s)" % s["mass_note"][0])
+        lap = anneal1.laplace(beta=-1)
+        sig = np.sqrt(np.reshape(lap["param_cov"], (-1,)))
+        km, ks = np.reshape(s["mean"], (-1, N_model * D + 1))[:, -1], np.reshape(s["std"], (-1, N_model * D + 1))[:, -1]
+        print("\n%d samples per chain, 10 leapfrog steps each:" % args.sample)
+        for b in range(km.size):
+            print("seed %d   k = %.4f +- %.2e from the chain   (Laplace sigma %.2e)   acceptance %.2f   divergent %d"
+                  % (b, km[b], ks[b], sig[b], np.ravel(s["accept_rate"])[b], np.ravel(s["n_divergent"])[b]))
 
     anneal1.save_paths(os.path.join(args.out, "paths.npy"))
     anneal1.save_params(os.path.join(args.out, "params.npy"))

@@ -279,6 +279,34 @@ int va_predict_tangent(va_handle h, const double *x0, const double *p, const dou
                        int32_t n_steps, int32_t substeps, int32_t every, const double *stim, double *out, double *dX,
                        double *var, double *cov);
 
+/* Sample exp(-A(X, p)) at one rf_scale: B Hamiltonian Monte Carlo chains, one per seed of the handle, on the device
+ * (csrc/va_hmc.h).  An iteration draws a momentum p = z / sqrt(minv), runs n_leap leapfrog steps of size
+ * eps_it = eps[b] (1 + jitter (2 u - 1)) -- n_leap evaluations by the handle's own evaluation kernel, an element-wise launch
+ * between two of them -- and accepts iff log(u_acc) < -dH, dH = (A1 + K1) - (A0 + K0), K = 1/2 sum p^2 minv.  A non-finite
+ * dH is a rejection (counted in n_divergent); a rejected iteration leaves the chain where it was.
+ *   XP [B*ld] in: start points; out: the chains' final states (HOST or DEVICE, `mem`)
+ *   eps [B]; jitter in [0, 1); minv NULL (identity) or minv_n = n_var values shared by the chains, or B * n_var
+ *   seed: key of the counter-based generator (Philox4x32-10, counter (chain, iteration, element, stream)): the draws do not
+ *        depend on the launch geometry.  noise NULL, or [n_iter][B][n_var + 2] the caller's own numbers instead: n_var
+ *        standard normals, the accept uniform, the jitter uniform
+ *   thin, keep_idx [n_keep_idx] (indices into the path vector): kept [B][n_iter / thin][n_keep_idx] holds those entries of
+ *        the state after every thin-th iteration
+ *   mean, var [B*n_var] over the n_iter states (var: sample variance, 0 for n_iter = 1); A_trace, dH, accepted
+ *        [B*n_iter]; n_divergent [B].  All HOST, any may be NULL.  The same inputs give the same bits on every call.
+ * One rf_scale per call.  The handle's resident paths are saved and restored, its seeds left idle; the evaluations
+ * (B (n_iter n_leap + 1)) are counted as va_action_grad's.  Plain launches on the handle's stream.
+ * VA_EINVAL: n_iter, n_leap or thin < 1; an eps or minv entry not positive and finite; jitter outside [0, 1); a keep_idx
+ * outside [0, n_var); a minv_n that is neither n_var nor B * n_var.
+ * VA_EUNSUPPORTED: handles with box bounds, network handles. */
+int va_hmc(va_handle h, double *XP, int64_t ld, int32_t mem, double rf_scale, int32_t n_iter, int32_t n_leap, const double *eps,
+           double jitter, const double *minv, int64_t minv_n, uint64_t seed, const double *noise, int32_t thin,
+           const int64_t *keep_idx, int32_t n_keep_idx, double *mean, double *var, double *A_trace, double *dH, int32_t *accepted,
+           int32_t *n_divergent, double *kept);
+/* Exactly what va_hmc's kernels draw for (seed, chain, iteration), computed on the current device: words [(n + 1)*4] the
+ * generator's four words for each of the n elements and for the extra stream, normals [n], uniforms [2] (accept, jitter).
+ * HOST arrays, any may be NULL.  Needs no handle. */
+int va_hmc_noise(uint64_t seed, int32_t chain, int32_t iteration, int64_t n, uint32_t *words, double *normals, double *uniforms);
+
 /* Measurement hook for bench.py: `iters` complete S1 evaluations (the same launch va_action_grad
  * makes: A, me, fe and the full gradient are formed every time) on the resident paths (those of
  * the last va_action_grad / va_anneal call), bracketed by HIP events on the handle's stream;

@@ -213,6 +213,11 @@ def lib():
     L.va_blocktri_selinv.restype = C.c_int
     L.va_laplace.argtypes = [h, c_dp, c_dp, C.c_int32, C.c_int64, c_dp, C.c_int32, C.c_int32] + [c_dp] * 5 + [c_ip]
     L.va_laplace.restype = C.c_int
+    L.va_hmc.argtypes = [h, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32, c_dp, C.c_double, c_dp, C.c_int64,
+                         C.c_uint64, c_dp, C.c_int32, c_lp, C.c_int32, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip, c_dp]
+    L.va_hmc.restype = C.c_int
+    L.va_hmc_noise.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_uint32), c_dp, c_dp]
+    L.va_hmc_noise.restype = C.c_int
     L.va_eval_timed.argtypes = [h, C.c_double, C.c_int32, C.POINTER(C.c_float)]
     L.va_eval_timed_prepare.argtypes = [h, C.c_double, C.c_int32]
     L.va_get_counters.argtypes = [h, c_lp, c_lp, c_lp]
@@ -243,7 +248,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -286,6 +291,17 @@ def eval_plan(batch, D, N_model, disc, ne, ghost=0, rm_array=False, rm_full=Fals
     else:
         check(lib().va_eval_plan(C.byref(d), int(ne), int(ghost), out))
     return (out[0], out[1], out[2], out[3]) if out[0] else None
+
+
+def hmc_noise(seed, chain, iteration, n):
+    """What Problem.hmc's kernels draw for (seed, chain, iteration), from the device itself (va_hmc_noise): (words
+    (n + 1, 4) uint32 -- the generator's words of the n elements and of the extra stream --, normals (n,), uniforms (2,):
+    accept, jitter).  One row of hmc's `noise` is np.concatenate([normals, uniforms])."""
+    n = int(n)
+    words = np.empty((n + 1, 4), np.uint32); normals = np.empty(n); uniforms = np.empty(2)
+    check(lib().va_hmc_noise(int(seed) & (2 ** 64 - 1), int(chain), int(iteration), n, words.ctypes.data_as(C.POINTER(C.c_uint32)),
+                             normals.ctypes.data_as(c_dp), uniforms.ctypes.data_as(c_dp)))
+    return words, normals, uniforms
 
 
 _modules = {}
@@ -596,6 +612,38 @@ class Problem(object):
         check(self._L.va_laplace(self._h, ptr(XP), ptr(P), npts, n, ptr(rf), 1 if gauss_newton else 0, int(chunk_pts),
                                  ptr(out["var_x"]), ptr(out.get("cov_xx")), ptr(out.get("cov_px")), ptr(out["cov_pp"]),
                                  ptr(out["logdet"]), out["status"].ctypes.data_as(c_ip)))
+        return out
+
+    def hmc(self, XP, rf_scale, n_iter, n_leap, eps, jitter=0.0, minv=None, seed=0, noise=None, thin=1, keep_idx=None):
+        """B Hamiltonian Monte Carlo chains of exp(-A) at one rf_scale on the device (va_hmc; csrc/va_hmc.h), started at
+        XP (B, n_var).  eps: a step size, or one per chain; minv: None (identity), (n_var,) or (B, n_var); noise: None (the
+        generator keyed by `seed`) or (n_iter, B, n_var + 2) standard normals, accept uniform, jitter uniform; keep_idx:
+        path-vector entries kept after every thin-th iteration.  Returns a dict: x (B, n_var) the final states, mean, var
+        (B, n_var), A, dH, accepted (B, n_iter), n_divergent (B,), kept (B, n_iter // thin, len(keep_idx)).  The handle's
+        resident state is left as found."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("hmc: network handles are not sampled (ODE handles only)")
+        XP = self._xp(XP).copy()
+        B, n = self.B, self.n_var
+        n_iter, n_leap, thin = int(n_iter), int(n_leap), int(thin)
+        eps = np.ascontiguousarray(np.broadcast_to(_f64(eps).reshape(-1), (B,)))
+        if minv is not None:
+            minv = _f64(minv)
+            if minv.shape not in [(n,), (B, n)]:
+                raise ValueError("hmc: minv must have shape (n_var,) = (%d,) or (B, n_var) = (%d, %d), got %s" % (n, B, n, minv.shape))
+        if noise is not None:
+            noise = _f64(noise)
+            if noise.shape != (max(n_iter, 0), B, n + 2):
+                raise ValueError("hmc: noise must have shape (n_iter, B, n_var + 2) = (%d, %d, %d), got %s" % (n_iter, B, n + 2, noise.shape))
+        keep = np.ascontiguousarray(np.zeros(0) if keep_idx is None else keep_idx, dtype=np.int64).reshape(-1)
+        ni, nk = max(n_iter, 1), max(n_iter, 1) // max(thin, 1)
+        out = dict(x=XP, mean=np.empty((B, n)), var=np.empty((B, n)), A=np.empty((B, ni)), dH=np.empty((B, ni)),
+                   accepted=np.empty((B, ni), np.int32), n_divergent=np.empty(B, np.int32), kept=np.empty((B, nk, keep.size)))
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
+        check(self._L.va_hmc(self._h, XP.ctypes.data, n, MEM_HOST, float(rf_scale), n_iter, n_leap, ptr(eps), float(jitter), ptr(minv),
+                             0 if minv is None else minv.size, int(seed) & (2 ** 64 - 1), ptr(noise), thin, keep.ctypes.data_as(c_lp),
+                             keep.size, ptr(out["mean"]), ptr(out["var"]), ptr(out["A"]), ptr(out["dH"]),
+                             out["accepted"].ctypes.data_as(c_ip), out["n_divergent"].ctypes.data_as(c_ip), ptr(out["kept"])))
         return out
 
     def eval_timed_prepare(self, rf_scale, iters):

@@ -41,6 +41,7 @@
 #include "va_predict_tlm.h"
 #include "va_hvp.h"
 #include "va_selinv.h"
+#include "va_hmc.h"
 
 using namespace va;
 
@@ -1295,6 +1296,136 @@ int va_predict_tangent(va_handle h, const double *x0, const double *p, const dou
         HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
     }
     HIPCHK(hipGetLastError());
+    return VA_OK;
+}
+
+// Hamiltonian Monte Carlo on the resident paths (va_hmc.h): B chains of n_iter iterations at one rf_scale, n_leap evaluations
+// each through run_eval -- whatever kernel the handle evaluates with -- and one element-wise launch between two of them.
+// Plain launches on the handle's stream; the workspace is the call's own.  The handle's resident paths are saved and put
+// back device-to-device, the seeds are left idle as a fresh handle has them, the evaluations are booked as va_action_grad's.
+int va_hmc(va_handle h, double *XP, int64_t ld, int32_t mem, double rf_scale, int32_t n_iter, int32_t n_leap, const double *eps,
+           double jitter, const double *minv, int64_t minv_n, uint64_t seed, const double *noise, int32_t thin,
+           const int64_t *keep_idx, int32_t n_keep_idx, double *mean, double *var, double *A_trace, double *dH, int32_t *accepted,
+           int32_t *n_divergent, double *kept)
+{
+    TRY(check_xp(h, XP, ld, mem));
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "va_hmc: network handles are not sampled (ODE handles only)");
+    Dev &dv = h->dv;
+    const Dims &dm = dv.dm;
+    if (dm.bounded) return fail(VA_EUNSUPPORTED, "va_hmc: the handle has box bounds; a reflecting sampler is not implemented");
+    const long n_var = dm.ND + dm.NPest, B = dm.B;
+    char why[192];
+    if (hmc_check_args(n_var, B, n_iter, n_leap, thin, eps, jitter, minv, (long)minv_n, keep_idx, n_keep_idx, why, sizeof why))
+        return fail(VA_EINVAL, "va_hmc: %s", why);
+    if (!std::isfinite(rf_scale)) return fail(VA_EINVAL, "va_hmc: rf_scale is not finite");
+    HmcArgs a = {};
+    if (!plan_hmc(n_var, B, a.geo, why, sizeof why)) return fail(VA_EUNSUPPORTED, "va_hmc: %s", why);
+    HIPCHK(hipSetDevice(h->device));
+    // the inverse mass and its square root (IEEE on the host: the momentum is z / sqrt(minv) on every platform)
+    const bool per_chain = minv && minv_n == B * n_var && B > 1;
+    const size_t nm = per_chain ? (size_t)B * n_var : (size_t)n_var;
+    std::vector<double> mh(nm, 1.0), sh(nm, 1.0), dh((size_t)B * n_iter);      // (dh: the energy errors' way back, below)
+    if (minv) for (size_t i = 0; i < nm; ++i) { mh[i] = minv[i]; sh[i] = sqrt(minv[i]); }
+    // one allocation, zeroed: [save | p | xs | gs | minv | sminv | eps | noise | A_cur | part | mean | m2 | A_trace | dH | kept |
+    // keep_idx (int64) | accepted (int32)]
+    const size_t nv = (size_t)B * dm.ld, nn = noise ? (size_t)n_iter * B * (n_var + 2) : 0, nt = (size_t)B * n_iter,
+                 nk = (size_t)B * (n_iter / thin) * n_keep_idx, ns = (size_t)B * n_var;
+    const size_t total = 4 * nv + 2 * nm + B + nn + 2 * B + 2 * (size_t)a.geo.grid + 2 * ns + 2 * nt + nk + (size_t)n_keep_idx + (nt + 1) / 2 + 1;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * total));
+    // (last declared, first destroyed: the stream has consumed the host arrays above before they go, on every way out)
+    struct Free { double *q; hipStream_t s; ~Free() { (void)hipStreamSynchronize(s); (void)hipFree(q); } } guard{buf, h->stream};
+    HIPCHK(hipMemsetAsync(buf, 0, sizeof(double) * total, h->stream));
+    double *q = buf;
+    auto take = [&q](size_t n) { double *r = q; q += n; return r; };
+    double *save = take(nv), *minv_d = nullptr, *sminv_d = nullptr, *eps_d = nullptr, *noise_d = nullptr;
+    a.p = take(nv); a.xs = take(nv); a.gs = take(nv);
+    minv_d = take(nm); sminv_d = take(nm); eps_d = take(B); noise_d = take(nn);
+    a.A_cur = take(2 * B); a.part = take(2 * (size_t)a.geo.grid); a.mean = take(ns); a.m2 = take(ns);
+    a.A_trace = take(nt); a.dH = take(nt); a.kept = take(nk);
+    int64_t *keep_d = (int64_t *)take(n_keep_idx);
+    a.accepted = (int32_t *)take((nt + 1) / 2);
+    HIPCHK(hipMemcpyAsync(minv_d, mh.data(), sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(sminv_d, sh.data(), sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(eps_d, eps, sizeof(double) * B, hipMemcpyHostToDevice, h->stream));
+    if (nn) HIPCHK(hipMemcpyAsync(noise_d, noise, sizeof(double) * nn, hipMemcpyHostToDevice, h->stream));
+    if (n_keep_idx) HIPCHK(hipMemcpyAsync(keep_d, keep_idx, sizeof(int64_t) * n_keep_idx, hipMemcpyHostToDevice, h->stream));
+    a.x = dv.x; a.g = dv.gt; a.minv = minv_d; a.sminv = sminv_d; a.minv_stride = per_chain ? n_var : 0; a.eps = eps_d; a.jitter = jitter;
+    a.noise = nn ? noise_d : nullptr; a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.chain0 = 0u; a.A_eval = dv.outA;
+    a.keep_idx = keep_d; a.n_keep = n_keep_idx; a.ld = dm.ld; a.n_var = n_var; a.B = (int)B; a.n_iter = n_iter; a.thin = thin;
+    // the resident paths aside, the caller's in; the start point's action and gradient
+    HIPCHK(hipMemcpyAsync(save, dv.x, sizeof(double) * nv, hipMemcpyDeviceToDevice, h->stream));
+    // whatever ends the sampling from here on, the handle goes back to what it was: paths restored, seeds idle,
+    // evaluations booked
+    int64_t n_evals = 0;
+    auto leave = [&]() {
+        (void)hipMemcpyAsync(dv.x, save, sizeof(double) * nv, hipMemcpyDeviceToDevice, h->stream);
+        launch_init_states(dv, PH_IDLE, 1.0, h->stream);
+        h->timed_armed_rf = -1.0;
+        h->n_eval_launch += n_evals; h->n_seed_evals += n_evals * B; h->n_seed_evals_direct += n_evals * B;
+    };
+    if (int rc_in = copy_in(h, XP, ld, mem)) { leave(); return rc_in; }      // (a failed copy may have overwritten part of dv.x)
+    launch_init_states(dv, PH_START, rf_scale, h->stream);
+    h->timed_armed_rf = rf_scale;
+    run_eval(h, EPI_FINALIZE); ++n_evals;
+    hipError_t e = hipMemcpyAsync(a.A_cur, dv.outA, sizeof(double) * B, hipMemcpyDeviceToDevice, h->stream);
+    for (int it = 0; it < n_iter && e == hipSuccess; ++it) {
+        a.it = it;
+        e = launch_hmc(a, HMC_BEGIN, h->stream);
+        for (int l = 0; l < n_leap && e == hipSuccess; ++l) {
+            if (l) e = launch_hmc(a, HMC_MID, h->stream);
+            if (e == hipSuccess) { run_eval(h, EPI_FINALIZE); ++n_evals; e = hipGetLastError(); }
+        }
+        if (e == hipSuccess) e = launch_hmc(a, HMC_END, h->stream);
+        if (e == hipSuccess) e = launch_hmc(a, HMC_COMMIT, h->stream);
+    }
+    if (e != hipSuccess) {
+        leave();
+        return fail(VA_EHIP, "va_hmc launch: %s", hipGetErrorString(e));
+    }
+    int rc = copy_out(h, dv.x, XP, ld, mem);
+    leave();
+    if (rc) return rc;
+    if (mean) HIPCHK(hipMemcpyAsync(mean, a.mean, sizeof(double) * ns, hipMemcpyDeviceToHost, h->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, a.m2, sizeof(double) * ns, hipMemcpyDeviceToHost, h->stream));
+    if (A_trace) HIPCHK(hipMemcpyAsync(A_trace, a.A_trace, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(dh.data(), a.dH, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
+    if (accepted) HIPCHK(hipMemcpyAsync(accepted, a.accepted, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, h->stream));
+    if (kept && nk) HIPCHK(hipMemcpyAsync(kept, a.kept, sizeof(double) * nk, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    // sample variance from the sum of squared deviations; a non-finite dH was a rejection and counts as divergent
+    if (var) for (size_t i = 0; i < ns; ++i) var[i] = n_iter > 1 ? var[i] / (double)(n_iter - 1) : 0.0;
+    for (long b = 0; b < B; ++b) {
+        int nd = 0;
+        for (int it = 0; it < n_iter; ++it) {
+            const double v = dh[(size_t)b * n_iter + it];
+            if (!std::isfinite(v)) ++nd;
+            if (dH) dH[(size_t)b * n_iter + it] = v;
+        }
+        if (n_divergent) n_divergent[b] = nd;
+    }
+    return VA_OK;
+}
+
+// What the sampler's kernels draw for (seed, chain, iteration), computed by the device they would run on (the current one):
+// words [(n + 1) * 4] the Philox words of the n element counters and of the extra stream's, normals [n], uniforms [2] (accept,
+// jitter); any may be NULL.  HOST arrays.
+int va_hmc_noise(uint64_t seed, int32_t chain, int32_t iteration, int64_t n, uint32_t *words, double *normals, double *uniforms)
+{
+    if (chain < 0 || iteration < 0 || n < 0 || n > 2147483647LL) return fail(VA_EINVAL, "va_hmc_noise: chain, iteration and n must not be negative (n below 2^31)");
+    const size_t nw = ((size_t)n + 1) * 4;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * ((size_t)n + 2) + sizeof(uint32_t) * nw));
+    struct Free { double *q; ~Free() { (void)hipDeviceSynchronize(); (void)hipFree(q); } } guard{buf};
+    double *nrm_d = buf, *uni_d = buf + n;
+    uint32_t *w_d = (uint32_t *)(buf + n + 2);
+    const hipError_t e = launch_hmc_noise((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)chain, (uint32_t)iteration, (long)n, w_d, nrm_d, uni_d, nullptr);
+    if (e != hipSuccess) return fail(VA_EHIP, "k_hmc_noise launch: %s", hipGetErrorString(e));
+    HIPCHK(hipDeviceSynchronize());
+    if (words) HIPCHK(hipMemcpy(words, w_d, sizeof(uint32_t) * nw, hipMemcpyDeviceToHost));
+    if (normals && n) HIPCHK(hipMemcpy(normals, nrm_d, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (uniforms) HIPCHK(hipMemcpy(uniforms, uni_d, sizeof(double) * 2, hipMemcpyDeviceToHost));
     return VA_OK;
 }
 

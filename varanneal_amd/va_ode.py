@@ -48,6 +48,18 @@ from ._ladder import LadderAnnealer
 _DISCS = ("euler", "trapezoid", "SimpsonHermite", "forwardmap")
 
 
+def hmc_rescale_step(eps, accept_rate, target=0.8):
+    """Warm-up rule of Annealer.sample: every chain's step size times 2^((rate - target) / (1 - target)) above the target
+    acceptance rate and 2^((rate - target) / target) below it -- 1 at the target, monotone in the rate, never more than a
+    factor 2 either way per block.  A pure function of (eps, accept_rate): new array, inputs untouched."""
+    eps = np.asarray(eps, dtype=np.float64)
+    rate = np.asarray(accept_rate, dtype=np.float64)
+    if not 0.0 < target < 1.0 or np.any(rate < 0.0) or np.any(rate > 1.0) or np.any(~np.isfinite(rate)):
+        raise ValueError("acceptance rates and the target lie in [0, 1] (target strictly inside)")
+    d = rate - target
+    return eps * np.exp2(np.where(d >= 0.0, d / (1.0 - target), d / target))
+
+
 class Annealer(LadderAnnealer):
     _print_exit_message = True
 
@@ -611,6 +623,124 @@ class Annealer(LadderAnnealer):
             cov[bad] = np.nan
             out["cov"] = cov.reshape(lead + (n_out, D, D))
         return out
+
+    # ------------------------------------------------------------------ sampling exp(-A) at a rung
+    def _hmc_mass(self, mass, k):
+        """(minv (B, n_var) or None for identity, reason or None) for rung k"""
+        n_var = self._NX + len(self._estpos)
+        if isinstance(mass, str):
+            if mass == 'identity':
+                return None, None
+            if mass != 'laplace':
+                raise ValueError("mass must be 'laplace', 'identity' or an array of inverse masses")
+            try:
+                lap = self.laplace(beta=[int(k)])
+            except (NotImplementedError, _capi.VaError) as e:
+                return None, "identity mass: laplace() refused (%s)" % e
+            sv = np.asarray(lap["state_var"]).reshape(self.B, self._NX)
+            pc = np.asarray(lap["param_cov"]).reshape(self.B, self.NPest, self.NPest)
+            minv = np.concatenate([sv, np.diagonal(pc, axis1=1, axis2=2)], axis=1)
+            bad = ~np.all(np.isfinite(minv) & (minv > 0.0), axis=1)
+            if bad.all():
+                return None, "identity mass: the Hessian is not positive definite at any selected minimiser"
+            minv[bad] = 1.0
+            return minv, ("identity mass for seed(s) %s: the Hessian is not positive definite there" % [int(b) for b in np.flatnonzero(bad)]
+                          if bad.any() else None)
+        minv = np.asarray(mass, dtype=np.float64)
+        if minv.shape not in [(n_var,), (self.B, n_var)]:
+            raise ValueError("mass array must have shape (n_var,) = (%d,) or (B, n_var)" % n_var)
+        return minv, None
+
+    def sample(self, n_samples, beta=-1, seeds=None, n_leap=10, step_size=None, jitter=0.1, mass='laplace', warmup=0, thin=1,
+               seed=0, keep=None, warmup_block=25):
+        """Sample exp(-A(X, p)) at a rung of the ladder (after anneal()): Hamiltonian Monte Carlo on the device
+        (csrc/va_hmc.h), one chain per seed, started at the stored minimisers.  With `beta` a sequence, each rung continues
+        from the previous rung's final state (precision-annealing Monte Carlo); every rung has warm-up and statistics of
+        its own.  n_samples states are kept per chain, one every `thin` iterations of n_leap leapfrog steps.
+          step_size  a number or one per seed; None: n_var^-1/4 with mass='laplace', a hundredth of it otherwise -- use warmup
+          mass       'laplace': 1 / mass = laplace()'s state_var and parameter variances (identity, with the reason in
+                     'mass_note', wherever laplace refuses or is not finite); 'identity'; or an array (n_var,) / (B, n_var)
+          warmup     iterations before the statistics, in blocks of warmup_block; after each block every chain's step is
+                     rescaled by hmc_rescale_step(its acceptance rate).  They enter no statistic.
+          keep       path-vector entries kept per sample; None: the last time row and the estimated parameters
+        A is the action AS THE PACKAGE NORMALISES IT (see laplace()).  Returns a dict; leading axes as predict():
+          mean, std (..., n_var)   accept_rate, n_divergent, step_size (...)   A, dH (..., n_samples * thin)
+          x_last (..., n_samples, D), params (..., n_samples, NPest)  (keep=None)   or   kept (..., n_samples, len(keep))
+          x (..., n_var) the final states;  seeds, rungs: the selection;  mass_note: per rung, None or why identity was used.
+        Box bounds: NotImplementedError."""
+        if self._pb is None or not getattr(self, "initalized", False):
+            raise ValueError("sample() works after anneal() / anneal_init()")
+        n_samples, n_leap, thin, warmup, warmup_block = int(n_samples), int(n_leap), int(thin), int(warmup), int(warmup_block)
+        if n_samples < 1 or warmup < 0 or warmup_block < 1:
+            raise ValueError("n_samples and warmup_block must be at least 1, warmup not negative")
+        sb, kb = self._select(np.atleast_1d(beta), seeds)
+        B, NX, npe = self.B, self._NX, len(self._estpos)
+        n_var = NX + npe
+        if keep is None:
+            last = np.arange((self.N_model - 1) * self.D, self.N_model * self.D)
+            keep_idx = np.concatenate([last, NX + (np.arange(npe - self.NPest, npe) if self._tdp else np.arange(npe))])
+        else:
+            keep_idx = np.asarray(keep, dtype=np.int64).reshape(-1)
+        XP = None
+        calls = [0]
+
+        def call_seed():
+            calls[0] += 1
+            return (int(seed) + 0x9E3779B97F4A7C15 * calls[0]) & (2 ** 64 - 1)
+        res, notes = [], []
+        for k in kb:
+            rf = float(self._rf_scale[k])
+            if XP is None:
+                src = self._mp[:, k]
+                XP = np.concatenate([src[:, :NX], src[:, NX:][:, self._estpos]], axis=1)
+            minv, note = self._hmc_mass(mass, k)
+            notes.append(note)
+            if step_size is None:
+                eps = np.full(B, float(n_var) ** -0.25 * (1.0 if minv is not None else 0.01))
+            else:
+                eps = np.array(np.broadcast_to(np.asarray(step_size, dtype=np.float64).reshape(-1), (B,)))
+            done = 0
+            while done < warmup:
+                nb = min(warmup_block, warmup - done)
+                w = self._pb.hmc(XP, rf, nb, n_leap, eps, jitter=jitter, minv=minv, seed=call_seed())
+                XP, done = w["x"], done + nb
+                eps = hmc_rescale_step(eps, w["accepted"].mean(axis=1))
+            r = self._pb.hmc(XP, rf, n_samples * thin, n_leap, eps, jitter=jitter, minv=minv, seed=call_seed(), thin=thin, keep_idx=keep_idx)
+            XP = r["x"]
+            r["step_size"] = eps
+            res.append(r)
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        stack = lambda f: np.stack([f(r)[sb] for r in res], axis=1).reshape(lead + np.shape(f(res[0]))[1:])
+        out = dict(mean=stack(lambda r: r["mean"]), std=stack(lambda r: np.sqrt(r["var"])), accept_rate=stack(lambda r: r["accepted"].mean(axis=1)),
+                   A=stack(lambda r: r["A"]), dH=stack(lambda r: r["dH"]), n_divergent=stack(lambda r: r["n_divergent"]),
+                   step_size=stack(lambda r: r["step_size"]), x=stack(lambda r: r["x"]), seeds=sb, rungs=kb, mass_note=notes)
+        kept = stack(lambda r: r["kept"])
+        if keep is None:
+            out["x_last"], out["params"] = kept[..., :self.D], kept[..., self.D:]
+        else:
+            out["kept"] = kept
+        return out
+
+    def predict_ensemble(self, n_steps, samples, q=(0.025, 0.5, 0.975), **predict_kwargs):
+        """The non-linear counterpart of predict_spread(): every kept (x_last, params) of a sample() result (keep=None)
+        integrated forward by predict()'s RK4 kernel, all members in ONE device call.  The fixed parameters are the
+        sampled rung's.  Returns a dict: members (..., n_samples, n_out, D) and quantiles (len(q), ..., n_out, D) over the
+        members; leading axes as sample().  predict_kwargs: substeps, every, stim."""
+        if "x_last" not in samples:
+            raise ValueError("predict_ensemble needs a sample() result with keep=None (x_last and params)")
+        if self._tdp:
+            raise NotImplementedError("predict_ensemble: time-dependent parameters are not carried")
+        sb, kb = samples["seeds"], samples["rungs"]
+        D, NP, NX = self.D, self.NP, self._NX
+        x_last = np.asarray(samples["x_last"]).reshape(len(sb), len(kb), -1, D)
+        S = x_last.shape[2]
+        P = np.repeat(self._mp[sb][:, kb][:, :, None, NX:], S, axis=2)           # (B_sel, nbeta_sel, S, NP)
+        if self.NPest:
+            P[..., self.Pidx] = np.asarray(samples["params"]).reshape(len(sb), len(kb), S, self.NPest)
+        out = self._pb.predict(x_last.reshape(-1, D), P.reshape(-1, NP), n_steps, t0=float(self.t_model[-1]), **predict_kwargs)
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        members = out.reshape(lead + (S, out.shape[1], D))
+        return dict(members=members, quantiles=np.quantile(members, q, axis=len(lead)))
 
     def me_gaussian(self, X):
         """Measurement error of a path (va_ode.py:138-158); X may omit the parameters."""
