@@ -26,11 +26,12 @@ def host_hv(exe, tmpdir, c, tile_rows=0, gn=0, X=None, V=None):
     X = c["X"] if X is None else X
     V = c["V"] if V is None else V
     npts, nvec, n = V.shape
-    P = np.broadcast_to(np.asarray(c["P"], float), (npts, len(c["P"])))
+    P = np.asarray(c["P"], float)                           # [NP], or [npts, NP]: every point its own
+    P = np.broadcast_to(P, (npts, P.shape[-1]))
     stim, tm = c.get("stim"), c.get("t_model")
     nstim = 0 if stim is None else np.asarray(stim).reshape(c["N"], -1).shape[1]
     rm_arr, rf_arr = isinstance(c["RM"], np.ndarray), isinstance(c["RF0"], np.ndarray)
-    head = [c["D"], c["N"], DISC[c["disc"]], c["nskip"], repr(c["dt"]), repr(c["rf_scale"]), gn, tile_rows, npts, nvec, len(c["P"]),
+    head = [c["D"], c["N"], DISC[c["disc"]], c["nskip"], repr(c["dt"]), repr(c["rf_scale"]), gn, tile_rows, npts, nvec, P.shape[1],
             len(c["Pidx"]), nstim, int(tm is not None), len(c["Lidx"])] + list(c["Lidx"]) + list(c["Pidx"])
     txt = " ".join(str(v) for v in head) + "\n"
     txt += "%d\n" % rm_arr + _nums(c["RM"]) + "%d\n" % rf_arr + _nums(c["RF0"])

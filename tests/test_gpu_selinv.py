@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import _hess_ref as hr
+import _hess_torch_ref as tr
 import _selinv_ref as sr
 from varanneal_amd import _capi, codegen, twin, va_ode
 
@@ -126,8 +127,10 @@ def _l96(t, x, k):
 
 @pytest.mark.parametrize("disc", ["trapezoid", "SimpsonHermite"])
 def test_library_geometry_through_the_annealer(disc):
-    """D = 20, N = 41, one seed, two rungs: W = 20, K = 41, and W = 40, K = 21 with a padded last block.  laplace(full=True)
-    against numpy.linalg.inv of the dense Hessian the existing path assembles at the same rung (kappa from that matrix);
+    """D = 20, N = 41, one seed, two rungs: W = 20, K = 41, and W = 40, K = 21 with a padded last block.  The dense Hessian
+    action_hessian assembles at each rung's minimiser against dense() of tests/_hess_torch_ref.py, entrywise within
+    REL max |H_ref| (measured on an MI355X: 1.1e-16 .. 2.1e-16 of max |H_ref|); then laplace(full=True)
+    against numpy.linalg.inv of that assembled matrix (kappa from that matrix);
     param_cov against param_covariance(): both carry a first-order error of kappa 2.2e-16 max |Sigma|, so they agree
     within twice that."""
     D, N = 20, 41
@@ -143,6 +146,13 @@ def test_library_geometry_through_the_annealer(disc):
     assert r["param_cov"].shape == (2, 1, 1) and r["logdet"].shape == (2,) and list(r["status"]) == [0, 0]
     for k in range(2):
         H = a.action_hessian(beta=k, form='dense')
+        # that matrix is assembled from hess_vec: hold it, entry by entry, to a Hessian the kernel has no part in
+        xp, Pk, rf = a._minimiser(k, 0)
+        assert rf == 2.0 ** k
+        H_ref = tr.TorchAction(tr.l96, D, N, Y, Lidx, twin.DT, 4.0, 0.5 * 2.0 ** k, Pk, [0], disc).dense(xp)
+        herr = np.abs(H - H_ref).max() / np.abs(H_ref).max()
+        print("%s rung %d: dense Hessian vs the torch reference %.2e" % (disc, k, herr))
+        assert H.shape == H_ref.shape and herr <= hr.REL
         sr.check_time_rows("%s rung %d" % (disc, k), H, N, D, 1, r["state_var"][k], r["state_cov"][k], r["state_param_cov"][k],
                            r["param_cov"][k], r["logdet"][k])
         Sig, kappa, _ = sr.reference(H)
