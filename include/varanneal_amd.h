@@ -147,8 +147,7 @@ int va_problem_info(va_handle h, int64_t *n_var, int64_t *ld_internal, int32_t *
 #define VA_TUNE_FOLD 1       /* 1: the seed's last-arriving workgroup forms A / runs the line-search step inside the
                               * evaluation kernel (default while the grid is <= 8 workgroups per CU); 0: tail kernels */
 #define VA_TUNE_GRAD_SC1 2   /* 1: gradient stores write through (default with FOLD)                                   */
-#define VA_TUNE_PRIO 3       /* 1: later-dispatched workgroups of a CU issue at higher priority (default); 2: a seed's  */
-                             /* first and last tile (the edge variant of the rows phase) issue ahead; 0: no priorities */
+#define VA_TUNE_PRIO 3       /* retired (issue priorities in k_eval4, measured without effect): accepted and ignored     */
 #define VA_TUNE_GRAPH 4      /* 1: ladder cycles and timed evaluations are replayed from a hipGraph (default)        */
 #define VA_TUNE_PERSIST 5    /* 1: ladders of few seeds on short paths run as ONE launch of the persistent
                               * per-seed kernel (csrc/va_persist.h: every vector of the minimisation resident in LDS),
@@ -159,7 +158,14 @@ int va_problem_info(va_handle h, int64_t *n_var, int64_t *ld_internal, int32_t *
                                  * state-gradient products in one kernel (k_nnet_fb), 0 the separate k_nnet_fwd + k_nnet_bwd_x.
                                  * The library's own choice: 1 when blocks of 32 examples x seeds >= 2 x CUs and the activation is a
                                  * built-in other than softplus.  2 + t: as 1, the first workgroups' starts spread over t us (measurement) */
+#define VA_TUNE_WIDE 8           /* the wave-private kernel k_eval4: row groups (four waves, tile_rows rows, one row of partial sums)
+                                 * per workgroup.  0: one (4-wave workgroups, the default: the wider forms measured slower); 1: the
+                                 * planner's rule (as many as shared a CU, on single-round grids that still fill the device); 2, 3: that
+                                 * many, VA_EUNSUPPORTED when the run length has no such kernel.  The sums and their order do not change */
 int va_problem_tune(va_handle h, int32_t what, int32_t value);
+/* The evaluation kernel's launch: row groups per workgroup (1 on every kernel but k_eval4) and the workgroups of one
+ * launch, batch x workgroups per seed.  (va_problem_info's ntiles counts row groups.) */
+int va_problem_eval_grid(va_handle h, int32_t *row_groups_per_workgroup, int32_t *workgroups);
 /* 1 if va_anneal / va_minimize_lbfgs on this handle run the persistent per-seed kernel, with its geometry
  * (workgroups per seed, time rows per workgroup); 0 otherwise. */
 int va_problem_persistent(va_handle h, int32_t *workgroups_per_seed, int32_t *rows_per_workgroup);

@@ -231,6 +231,8 @@ def lib():
     L.va_read_eval_outputs.argtypes = [h, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     L.va_debug_read_partials.argtypes = [h, c_dp, C.c_int64]
     L.va_problem_eval_kernel.argtypes = [h, c_ip, c_ip]
+    L.va_problem_eval_grid.argtypes = [h, c_ip, c_ip]
+    L.va_problem_eval_grid.restype = C.c_int
     L.va_problem_tune.argtypes = [h, C.c_int32, C.c_int32]
     L.va_debug_read_persist.argtypes = [h, c_dp, C.c_int64]
     L.va_debug_read_persist.restype = C.c_int
@@ -246,7 +248,7 @@ def lib():
     return L
 
 
-EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_tune", "va_problem_create",
+EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_eval_grid", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
            "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
@@ -391,10 +393,14 @@ class Problem(object):
         check(self._L.va_problem_info(self._h, C.byref(nv), C.byref(ld), C.byref(T), C.byref(nt)))
         ek, rr = C.c_int32(), C.c_int32()
         check(self._L.va_problem_eval_kernel(self._h, C.byref(ek), C.byref(rr)))
+        # (k_eval4: tile_rows / ntiles describe a row group, the four waves that own one row of partial sums; a workgroup
+        # runs row_groups of them and eval_grid workgroups make one launch)
+        rg, wgs = C.c_int32(), C.c_int32()
+        check(self._L.va_problem_eval_grid(self._h, C.byref(rg), C.byref(wgs)))
         return dict(n_var=nv.value, ld=ld.value, tile_rows=T.value, ntiles=nt.value, eval_kernel=ek.value,
-                    run_rows=rr.value)
+                    run_rows=rr.value, row_groups=rg.value, eval_grid=wgs.value)
 
-    TUNE = {"fold": 1, "grad_sc1": 2, "prio": 3, "graph": 4, "persist": 5, "persist_rows": 6, "nnet_fused": 7}      # VA_TUNE_* of include/varanneal_amd.h
+    TUNE = {"fold": 1, "grad_sc1": 2, "prio": 3, "graph": 4, "persist": 5, "persist_rows": 6, "nnet_fused": 7, "wide": 8}      # VA_TUNE_* of include/varanneal_amd.h
 
     def debug_read_persist(self, n):
         out = np.empty(n)
@@ -409,7 +415,8 @@ class Problem(object):
         return (g.value, t.value) if on else None
 
     def tune(self, **knobs):
-        """performance knobs that change no result: fold= (tail inside the evaluation kernel), grad_sc1=, prio=, graph="""
+        """performance knobs that change no result: fold= (tail inside the evaluation kernel), grad_sc1=, graph=,
+        wide= (k_eval4's row groups per workgroup: 0 one (default), 1 the planner's rule, 2 / 3 that many); prio= is retired and ignored"""
         for k, v in knobs.items():
             check(self._L.va_problem_tune(self._h, self.TUNE[k], int(v)))
 

@@ -113,6 +113,7 @@ struct va_problem_s {
     bool is_nnet = false;              // feed-forward-network action (va_nnet.hip) instead of an ODE path
     bool fold = false;                 // the evaluation kernel runs the tail itself (last arriver of each seed)
     bool tune_graph = true;            // ladder cycles / timed evaluations replayed from a hipGraph (va_problem_tune)
+    int wg4_plan = 1;                  // k_eval4: the planner's row groups per workgroup (dv.wg4: what the handle runs, VA_TUNE_WIDE)
     hipGraphExec_t timed_gexec = nullptr;   // va_eval_timed's chunk of launches
     int timed_chunk = 0;
     Dev timed_dv;                      // the device image the chunk was captured with (kernels take it by value):
@@ -188,7 +189,8 @@ int alloc_solver_state(va_handle h)
     // x and d carry a zero-filled guard in front and behind: the evaluation kernels stage whole
     // tiles (+ halo rows) without clamping, so the first / last tile of the first / last seed reads
     // up to one tile beyond its path (such rows are masked out of the arithmetic)
-    const size_t guard = (((size_t)(dm.T + 8) * dm.D + 15) / 16) * 16;
+    // (k_eval4: a workgroup of up to three row groups, whatever VA_TUNE_WIDE asks for later)
+    const size_t guard = (((size_t)((dm.emode == 4 ? 3 : 1) * dm.T + 8) * dm.D + 15) / 16) * 16;
     TRY(h->alloc(&dv.x, B * ld + 2 * guard)); TRY(h->alloc(&dv.g, B * ld));
     TRY(h->alloc(&dv.gt, B * ld)); TRY(h->alloc(&dv.d, B * ld + 2 * guard));
     dv.x += guard; dv.d += guard;
@@ -595,7 +597,7 @@ int plan_problem(va_handle h, const va_problem_desc *d, const UserRhs *user, Eva
         builtin_rhs_table(h->rt);
         builtin_hvp_table(h->rt_hvp);
         EvalForm l96;
-        l96.ne = RhsL96s::NE; l96.ghost = RhsL96g::GHOST; l96.has_reach5 = true;
+        l96.ne = RhsL96s::NE; l96.nb = RhsL96s::NB; l96.ghost = RhsL96g::GHOST; l96.has_reach5 = true;
         l96.reach5[0] = t5_xl<RhsL96s>(); l96.reach5[1] = t5_xr<RhsL96s>(); l96.reach5[2] = t5_gl<RhsL96s>(); l96.reach5[3] = t5_gr<RhsL96s>();
         plan = plan_eval(d, l96);
         return VA_OK;
@@ -610,6 +612,15 @@ int plan_problem(va_handle h, const va_problem_desc *d, const UserRhs *user, Eva
     dv.cps = mp.cps; dv.cpv = mp.cpv;
     dv.cpnsg = (mp.cpv && plan.emode == 5) ? plan.g5.NSG : 0;
     return VA_OK;
+}
+
+// k_eval4's workgroup width and what follows from it: G row groups per workgroup, nwg = ceil(ntiles / G) workgroups per
+// seed (nwg <= ntiles, so the 2^32 bound fill_dims checks covers every G)
+void set_eval4_groups(Dev &dv, int G)
+{
+    dv.wg4 = G;
+    const int nwg = eval4_nwg(dv);
+    dv.nwg_magic = (unsigned)(((1ull << 32) + nwg - 1) / nwg);
 }
 
 // Step 3: Dims and the rest of Dev that follow from the descriptor and the plan
@@ -628,12 +639,13 @@ int fill_dims(va_handle h, const va_problem_desc *d, const EvalPlan &plan)
     dm.emode = plan.emode; dm.RY = plan.RY; dm.NT = plan.NT; dm.maxr = plan.maxr; dm.T = plan.T; dm.ntiles = plan.ntiles;
     dm.ghost = plan.ghost;
     dv.g4 = plan.g4; dv.g5 = plan.g5;
-    if (dm.emode == 4 && (unsigned long long)dm.B * dm.ntiles * dm.ntiles >= (1ull << 32))      // (umulhi by ntiles_magic would no longer be an exact division)
+    if (dm.emode == 4 && (unsigned long long)dm.B * dm.ntiles * dm.ntiles >= (1ull << 32))      // (umulhi by nwg_magic would no longer be an exact division)
         return fail(VA_EUNSUPPORTED, "batch x tiles too large for the wave-private kernel: pass eval_kernel=3");
-    dv.ntiles_magic = (unsigned)(((1ull << 32) + dm.ntiles - 1) / dm.ntiles);
+    h->wg4_plan = dm.emode == 4 ? plan.wg4 : 1;
+    set_eval4_groups(dv, EVAL4_WIDE_DEFAULT ? h->wg4_plan : 1);
     // fold the tail into the evaluation kernel while the whole grid is resident at once (<= 8 workgroups per CU)
     h->fold = (long)dm.B * dm.ntiles <= 8L * 256;
-    dm.nprow = dm.ntiles;                                                    // one partial row per workgroup
+    dm.nprow = dm.ntiles;                                                    // one partial row per workgroup (k_eval4: per row group)
     dm.dt = d->dt_model;
     dm.cme = d->L > 0 ? 1.0 / ((double)dm.L * dm.N_data) : 0.0;
     dm.cfe = 1.0 / ((double)dm.D * (dm.N - 1));
@@ -643,7 +655,6 @@ int fill_dims(va_handle h, const va_problem_desc *d, const EvalPlan &plan)
     // write-through gradient stores pay where the grid is one resident round and the end-of-kernel write-back
     // of 10 MB is on the critical path (C3: -1.3 us); on large grids they cost 10 % (4096 seeds: 446 vs 404 us)
     dv.gaux = h->fold ? 1 : 0;
-    dv.prio = 1;
     return VA_OK;
 }
 
@@ -977,6 +988,8 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
         vinfo(uv);
         u.variant = ModuleVariant::decode(uv);
         if (!t.eval_var) u.variant.kernel = 0;
+        typedef int (*nb_fn)(void);
+        if (nb_fn nb = (nb_fn)dlsym(u.dl, "va_user_col_neighbours")) u.variant.nb = nb();
     }
     if (info_fn cmap = (info_fn)dlsym(u.dl, "va_user_colp_map")) {
         // (S <= RHS_MAX_NP and V <= CP_VMAX by construction: the generator checks both)
@@ -1094,6 +1107,15 @@ int va_problem_info(va_handle h, int64_t *n_var, int64_t *ld_internal, int32_t *
     if (ld_internal) *ld_internal = h->dv.dm.ld;
     if (tile_rows) *tile_rows = h->dv.dm.T;
     if (ntiles) *ntiles = h->dv.dm.ntiles;
+    return VA_OK;
+}
+
+int va_problem_eval_grid(va_handle h, int32_t *row_groups_per_workgroup, int32_t *workgroups)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    const bool e4 = !h->is_nnet && h->dv.dm.emode == 4;
+    if (row_groups_per_workgroup) *row_groups_per_workgroup = e4 ? eval4_groups(h->dv) : 1;
+    if (workgroups) *workgroups = h->is_nnet ? 0 : h->dv.dm.B * (e4 ? eval4_nwg(h->dv) : h->dv.dm.ntiles);
     return VA_OK;
 }
 
@@ -1754,7 +1776,27 @@ int va_problem_tune(va_handle h, int32_t what, int32_t value)
         if (h->is_nnet) return fail(VA_EUNSUPPORTED, "the network action chooses its tail by the net's size");
         h->fold = value != 0; break;
     case VA_TUNE_GRAD_SC1: h->dv.gaux = value != 0 ? 1 : 0; break;
-    case VA_TUNE_PRIO: h->dv.prio = value < 0 ? 0 : (value > 2 ? 2 : value); break;
+    case VA_TUNE_PRIO: break;       // (retired with the kernel's priority branches: accepted, nothing to set)
+    case VA_TUNE_WIDE: {
+        // 0: 4-wave workgroups; 1: the planner's width; 2, 3: that many row groups per workgroup, if the kernel has them
+        if (h->is_nnet || h->dv.dm.emode != 4) {
+            if (value > 1) return fail(VA_EUNSUPPORTED, "only the wave-private kernel k_eval4 has wide workgroups");
+            break;
+        }
+        if (value < 0 || value > 3) return fail(VA_EINVAL, "wide = %d: 0, 1 (the planner's choice), 2 or 3 row groups per workgroup", value);
+        HIPCHK(hipSetDevice(h->device));
+        const int was = h->dv.wg4;
+        set_eval4_groups(h->dv, value == 0 ? 1 : (value == 1 ? h->wg4_plan : value));
+        EvalOp op{true, nullptr, hipSuccess};
+        if (eval_lds_bytes(h->dv) > LDS_OPTIN_BYTES) op.err = hipErrorInvalidValue;
+        else h->rt.eval(h->dv, op);         // (the wider kernel's own opt-in to its LDS; refuses a width the run length has no kernel for)
+        if (op.err != hipSuccess) {
+            set_eval4_groups(h->dv, was);
+            (void)hipGetLastError();
+            return fail(VA_EUNSUPPORTED, "k_eval4 at runs of %d rows has no workgroup of %d row groups (registers or LDS)", h->dv.dm.maxr, value);
+        }
+        break;
+    }
     case VA_TUNE_GRAPH: h->tune_graph = value != 0; break;
     case VA_TUNE_NNET_FUSED:
         if (!h->is_nnet || !h->nn.Wf) return fail(VA_ESTATE, "not a network handle whose layers fit the fused kernel");

@@ -39,9 +39,9 @@ struct Dev {
     const int *ystrip;             // [NS][2] per strip: first data column staged (even), 16-byte pieces per observation row
     int lsrun;                     // this launch may hold line-search points (seeds in PH_LS): stage d as well
     int epi;                       // EPI_*: tail folded into the evaluation kernel
-    unsigned ntiles_magic;         // floor(w / ntiles) == umulhi(w, ntiles_magic) for w < B*ntiles
+    unsigned nwg_magic;            // k_eval4: floor(w / nwg) == umulhi(w, nwg_magic) for w < B*nwg, nwg = eval4_nwg(dv) workgroups per seed
     int gaux;                      // 1: gradient stores write through (sc1)
-    int prio;                      // 1: later-dispatched workgroups of a CU issue at higher priority
+    int wg4;                       // k_eval4: row groups (of 4 waves, Geo4::T rows) per workgroup, 1 .. 3 (0 reads as 1)
     int sticky;                    // measurement only (va_lbfgs_timed): last arrivers leave upd / dir set
     int evcols;                    // 8, 16 or 32 >= EP_GP + NP: columns of the eval partial rows in use
     ProblemPtrs pp;
@@ -92,10 +92,18 @@ struct EvalOp { bool prepare; hipStream_t s; hipError_t err; };
 constexpr size_t LDS_DEFAULT_BYTES = 64 * 1024, LDS_OPTIN_BYTES = 160 * 1024;      // without / with the opt-in: a CU's whole LDS
 
 // (a multiple of 8: xcd_swizzle deals the workgroups over the 8 XCDs)
-inline int eval_grid(const Dims &dm) { return ((dm.B * dm.ntiles + 7) / 8) * 8; }
+inline int eval_grid(int nwork) { return ((nwork + 7) / 8) * 8; }
+inline int eval_grid(const Dims &dm) { return eval_grid(dm.B * dm.ntiles); }
 
+// k_eval4's two counts: dm.ntiles (= dm.nprow) is the seed's ROW GROUPS -- the 4-wave units of Geo4::T rows that each own a
+// row of the partial tables, what the epilogue reduces over -- and a workgroup runs wg4 consecutive ones, so the grid,
+// the decoding of blockIdx and the arrival count go by the seed's WORKGROUPS
+VA_HD int eval4_groups(const Dev &dv) { return dv.wg4 > 1 ? dv.wg4 : 1; }
+VA_HD int eval4_nwg(const Dev &dv) { return (dv.dm.ntiles + eval4_groups(dv) - 1) / eval4_groups(dv); }
+
+// (grid < 0: one workgroup per tile, eval_grid(dv.dm))
 template <class KERNEL>
-inline void eval_op(KERNEL kern, const Dev &dv, int threads, size_t lds, EvalOp &op)
+inline void eval_op(KERNEL kern, const Dev &dv, int threads, size_t lds, EvalOp &op, int grid = -1)
 {
     if (op.prepare) {
         if (lds <= LDS_DEFAULT_BYTES) return;
@@ -103,7 +111,7 @@ inline void eval_op(KERNEL kern, const Dev &dv, int threads, size_t lds, EvalOp 
         if (e != hipSuccess) op.err = e;
         return;
     }
-    hipLaunchKernelGGL(kern, dim3(eval_grid(dv.dm)), dim3(threads), lds, op.s, dv);
+    hipLaunchKernelGGL(kern, dim3(grid < 0 ? eval_grid(dv.dm) : grid), dim3(threads), lds, op.s, dv);
 }
 
 // the run-time discretisation as a compile-time constant: f(std::integral_constant<int, DISC_*>)
@@ -160,6 +168,9 @@ size_t update_lds_bytes(const Dims &dm);
 // bounded problems: L-BFGS-B's direction step in k_direction's place (va_lbfgsb.hip)
 void launch_lbfgsb_dir(const Dev &dv, hipStream_t s);
 hipError_t prepare_lbfgsb(const Dev &dv);
+// the built-in right-hand side on k_eval4's wider workgroups (va_eval4_g2.hip, va_eval4_g3.hip)
+void eval4_builtin_g2(const Dev &dv, EvalOp &op);
+void eval4_builtin_g3(const Dev &dv, EvalOp &op);
 // streaming column strips for the built-in right-hand side (va_eval5.hip)
 void eval5_builtin(const Dev &dv, EvalOp &op);
 size_t eval5_lds(const Dev &dv);

@@ -1,4 +1,4 @@
-// va_eval4.h -- the wave-private column-run evaluation kernel k_eval4<RHS, DISC, K, D, W_SCALAR, SUB> and
+// va_eval4.h -- the wave-private column-run evaluation kernel k_eval4<RHS, DISC, K, D, W_SCALAR, SUB, G> and
 // its launcher, as a header: compiled into libvaranneal_amd.so for the built-in Lorenz-96 and into
 // every generated right-hand-side module whose model has a column form (varanneal_amd/codegen.py:
 // translation-invariant stencils, or small dense systems such as the tutorial's NaKL neuron).
@@ -31,16 +31,27 @@ __device__ __forceinline__ void tile4_dma(const Geo4 &g, const double *src, doub
 // all images are requested up front, the first sub-tile's gradient leaves while the next is computed
 // (co-resident waves run in lockstep: load, then compute, then store, all of them together), and
 // the wave reduces its partial sums once.
-template <class RHS, int DISC, int K, int DC, int WS, int SUB>
-__global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ? 3 : 2)) void k_eval4(const Dev dv)      // (the neighbour values of the lane's K rows live in registers: K * NB of them)
+// 4-wave workgroups of this instantiation a CU holds (by registers): the neighbour values of the lane's K rows live in
+// registers, K * NB of them
+constexpr int eval4_wpc(int K, int NB) { return (K <= 7 && K * NB <= 28) ? 3 : 2; }
+
+// G: row groups per workgroup.  A row group is four waves = Geo4::T rows of the path and owns one row of the partial
+// tables; a workgroup is G consecutive ones (wave w: row group w / 4), 256 G threads on the register budget of the
+// 4-wave form, so G <= eval4_wpc: G of the 4-wave workgroups that would share a CU become one, with ONE publishing wave,
+// one arrival and one dispatch between them.  G = 1 is the 4-wave kernel itself.
+template <class RHS, int DISC, int K, int DC, int WS, int SUB, int G>
+__global__ __launch_bounds__(256 * G, SUB > 1 ? 1 : eval4_wpc(K, RHS::NB)) void k_eval4(const Dev dv)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    static_assert(G >= 1 && G <= eval4_wpc(K, RHS::NB), "a workgroup of G row groups lives on the registers of G 4-wave workgroups of one CU");
     constexpr bool W_SCALAR = WS != 0;                        // WS: 0 weight arrays, 1 scalar weights, 2 scalar weights + merr_nskip
     const Dims &dm = dv.dm;
-    const int nwork = dm.B * dm.ntiles;
+    const int nwg = G == 1 ? dm.ntiles : (dm.ntiles + G - 1) / G;        // workgroups per seed (dm.ntiles: row groups per seed)
+    const int nwork = dm.B * nwg;
     const int w = xcd_swizzle(blockIdx.x, nwork);
     if (w >= nwork) return;
-    const int b = dm.ntiles > 1 ? (int)__umulhi((unsigned)w, dv.ntiles_magic) : w, tile = w - b * dm.ntiles;
+    const int b = nwg > 1 ? (int)__umulhi((unsigned)w, dv.nwg_magic) : w, wg = w - b * nwg;
+    const int tile = wg * G;                                  // the workgroup's first row group
 
     constexpr int HL = Halo<DISC>::HL, HR = Halo<DISC>::HR, NE = RHS::NE;
     constexpr int NV = EP_GP + RHS::NP;
@@ -188,19 +199,6 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the wave's images have landed
     __builtin_amdgcn_wave_barrier();
     VA_E4_STAMP(2);
-    // Workgroups that share a CU start together and their data arrives in dispatch order; the later
-    // ones then compete for the vector pipe with workgroups already in their gather / reduction
-    // phases and finish up to 1.7 us after the first.  The kernel is as long as its last workgroup:
-    // later workgroups issue at higher priority.
-    if (dv.prio == 1) {
-        const int grp = (int)(blockIdx.x >> 8);
-        if (grp == 1) __builtin_amdgcn_s_setprio(1);
-        else if (grp >= 2) __builtin_amdgcn_s_setprio(2);
-    } else if (dv.prio == 2) {
-        // the seed's first and last tile run the edge variant of the rows phase (+0.5 us, profiles/r04_timeline_c3.txt) and
-        // are the workgroups a seed's tail waits for: they issue ahead of the CU's other workgroups
-        if (tile == 0 || tile == dm.ntiles - 1) __builtin_amdgcn_s_setprio(3);
-    }
     if (use_d) {
         // trial point x + stp*d in place (the same fma as k_update's accepted iterate), then the
         // lane's own entries of d for the g.d partial; the d images are dead after that
@@ -235,9 +233,9 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
     }
     unsigned old = 0;
     double gvv[SUB][K];                       // the gradient stays in registers until the partial sums are out
-    // The workgroup's row of partial sums: every wave reduces through the matrix pipe (max|g| through
-    // DPP row moves) and lane 0 leaves the totals in the wave's LDS strip; after a workgroup barrier
-    // wave 0 adds the four waves' values in a fixed order and stores ONE row (write-through).
+    // The workgroup's rows of partial sums: every wave reduces through the matrix pipe (max|g| through
+    // DPP row moves) and lane 0 leaves the totals in the wave's LDS strip; after ONE workgroup barrier
+    // wave 0 adds each row group's four waves in a fixed order and stores a row per row group (write-through).
     auto publish = [&]() {
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
@@ -261,18 +259,29 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
         __builtin_amdgcn_s_barrier();
         VA_E4_STAMP(6);
         if (wave == 0) {
-            if (lane < NV) {
-                const double r0 = strip[lane], r1 = strip[g.WAVE + lane], r2 = strip[2 * g.WAVE + lane], r3 = strip[3 * g.WAVE + lane];
-                double v = (lane == EP_GMAX) ? fmax(fmax(r0, r1), fmax(r2, r3)) : ((r0 + r1) + r2) + r3;
-                if ((lane == EP_GTD && !use_d) || ((lane == EP_GTD || lane == EP_GN2 || lane == EP_GMAX) && !lsq)) v = 0.0;
-                st_sc1(dv.evp + ((size_t)b * dm.ntiles + tile) * EP_N + lane, v);
+            // lane q NV + k: column k of row group tile + q (row groups past the seed's last own no row)
+#pragma unroll
+            for (int e0 = 0; e0 < G * NV; e0 += 64) {
+                const int e = e0 + lane, q = G == 1 ? 0 : e / NV, k = e - q * NV;
+                if (e < G * NV && (G == 1 || tile + q < dm.ntiles)) {
+                    const double *sq = strip + 4 * q * g.WAVE + k;
+                    const double r0 = sq[0], r1 = sq[g.WAVE], r2 = sq[2 * g.WAVE], r3 = sq[3 * g.WAVE];
+                    double v = (k == EP_GMAX) ? fmax(fmax(r0, r1), fmax(r2, r3)) : ((r0 + r1) + r2) + r3;
+                    if ((k == EP_GTD && !use_d) || ((k == EP_GTD || k == EP_GN2 || k == EP_GMAX) && !lsq)) v = 0.0;
+                    st_sc1(dv.evp + ((size_t)b * dm.ntiles + tile + q) * EP_N + k, v);
+                }
             }
             if constexpr (NCV > 0) {
-                // the workgroup's row of the vector table: the four waves added in wave order (write-through, as the row above)
-                double *vrow = dv.evv + ((size_t)b * dm.ntiles + tile) * dv.cpv;
-                for (int e = lane; e < NCV * D; e += 64) {
-                    const double r0 = smem[e], r1 = smem[g.WAVE + e], r2 = smem[2 * g.WAVE + e], r3 = smem[3 * g.WAVE + e];
-                    st_sc1(vrow + e, ((r0 + r1) + r2) + r3);
+                // the row groups' rows of the vector table: each one's four waves added in wave order (write-through, as the rows above)
+#pragma unroll
+                for (int q = 0; q < G; ++q) {
+                    if (G > 1 && tile + q >= dm.ntiles) break;
+                    double *vrow = dv.evv + ((size_t)b * dm.ntiles + tile + q) * dv.cpv;
+                    const double *sq = smem + 4 * q * g.WAVE;
+                    for (int e = lane; e < NCV * D; e += 64) {
+                        const double r0 = sq[e], r1 = sq[g.WAVE + e], r2 = sq[2 * g.WAVE + e], r3 = sq[3 * g.WAVE + e];
+                        st_sc1(vrow + e, ((r0 + r1) + r2) + r3);
+                    }
                 }
             }
         }
@@ -331,6 +340,9 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
         const int npieces = RK * D / 2;                       // 16-byte pieces of one sub-tile's rows
 #pragma unroll
         for (int s = 0; s < SUB; ++s) {
+            // (a wide workgroup's trailing row groups may start past the path: nothing of theirs to store, and the
+            // buffer's range check is not asked to judge a base beyond its end)
+            if (G > 1 && n0w + s * RK >= dm.N) break;
             wave_sync_lds();                                  // (the gather phase has read the products)
             if (active) {
 #pragma unroll
@@ -361,7 +373,7 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
     if (wave == 0 && dv.epi != EPI_NONE) {
         old = __builtin_amdgcn_readfirstlane(old);
         asm volatile("" ::: "memory");
-        last = old == (unsigned)dm.ntiles - 1u;
+        last = old == (unsigned)nwg - 1u;                     // (one arrival per workgroup)
         if (last) {
             if (lane == 0) __hip_atomic_store(dv.cnt_eval + (size_t)b * CNT_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             eval_epilogue<true, (NCV > 0)>(dv, b, lane, reinterpret_cast<SeedHot *>(xsw), dv.epi);
@@ -371,16 +383,30 @@ __global__ __launch_bounds__(256, SUB > 1 ? 1 : ((K <= 7 && K * RHS::NB <= 28) ?
 }
 
 
-inline size_t eval4_lds_bytes(const Dev &dv) { return sizeof(double) * (size_t)dv.g4.NW * dv.g4.WAVE; }
+// (Geo4::NW = 4 waves, one row group; the workgroup holds eval4_groups of them)
+inline size_t eval4_lds_bytes(const Dev &dv) { return sizeof(double) * (size_t)eval4_groups(dv) * dv.g4.NW * dv.g4.WAVE; }
 
 // launch or prepare one instantiation (the caller has checked that dv.g4 / dv.dm.maxr / dv.dm.disc match it).
 // Sub-tiles per wave: 1.  (Measured at C3, SUB = 3 -- one wave per SIMD, 256 workgroups -- against SUB = 1 -- three waves
 // per SIMD: 8.7 vs 8.0 us.  A lone wave has nothing to hide its LDS and matrix-pipe latencies behind, so only SUB = 1 is
 // compiled; the kernel keeps the loop.)
-template <class RHS, int DISC, int K, int DC, int WS>
+template <class RHS, int DISC, int K, int DC, int WS, int G>
 inline void eval4_op(const Dev &dv, EvalOp &op)
 {
-    eval_op(k_eval4<RHS, DISC, K, DC, WS, 1>, dv, 256, eval4_lds_bytes(dv), op);
+    if constexpr (G <= eval4_wpc(K, RHS::NB)) {
+        eval_op(k_eval4<RHS, DISC, K, DC, WS, 1, G>, dv, 256 * G, eval4_lds_bytes(dv), op, eval_grid(dv.dm.B * eval4_nwg(dv)));
+    } else op.err = hipErrorInvalidConfiguration;         // (no such kernel: the registers of this run length hold two row groups per CU)
+}
+// every width this instantiation has, chosen by dv.wg4 (a generated module's one translation unit)
+template <class RHS, int DISC, int K, int DC, int WS>
+inline void eval4_op_groups(const Dev &dv, EvalOp &op)
+{
+    switch (eval4_groups(dv)) {
+    case 1: eval4_op<RHS, DISC, K, DC, WS, 1>(dv, op); break;
+    case 2: eval4_op<RHS, DISC, K, DC, WS, 2>(dv, op); break;
+    case 3: eval4_op<RHS, DISC, K, DC, WS, 3>(dv, op); break;
+    default: op.err = hipErrorInvalidConfiguration; break;
+    }
 }
 
 }  // namespace va

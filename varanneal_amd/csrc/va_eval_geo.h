@@ -24,13 +24,15 @@ struct EvalForm {
     bool has_reach5 = false;    // the column form may run the streaming kernel (va_tile5.h), with these reaches
     int reach5[4] = {0, 0, 0, 0};      // {xl, xr, gl, gr}
     int lin = 0;                // the flat form carries a dense constant linear part (RHS::LINEAR): one more staged array
+    int nb = 0;                 // neighbour columns its column form reads (RhsL96s::NB; a module's RhsUserCol::NB), or 0: not known
 };
 
 // The chosen kernel and its geometry: what va_problem_create copies into the device image.
 struct EvalPlan {
     int emode = 0, RY = 0, NT = 0, maxr = 0, T = 0, ntiles = 0;      // as Dims (va_core.h)
     int ghost = 2;
-    Geo4 g4{};                  // emode 4
+    Geo4 g4{};                  // emode 4, with
+    int wg4 = 1;                //   row groups (ntiles counts them: 4 waves, g4.T rows, one row of the partial tables) per workgroup
     Geo5 g5{};                  // emode 5, with
     std::vector<int> ystrip;    //   [NS][2] per strip: first data column staged (even), 16-byte pieces per observation row
 };
@@ -119,6 +121,35 @@ inline bool plan_eval5(const va_problem_desc *d, const EvalForm &f, EvalPlan &p)
     return true;
 }
 
+// 4-wave workgroups of k_eval4 a CU holds, by registers (eval4_wpc, va_eval4.h); a column form whose neighbour count
+// is not known counts as the smaller
+inline int eval4_per_cu(int K, int nb) { return (nb > 0 && K <= 7 && K * nb <= 28) ? 3 : 2; }
+
+constexpr int EVAL4_CUS = 256;              // (the device the planners' round arithmetic is written for)
+// Does a handle start on the width plan_eval4_groups chooses?  No: measured at C3 (64 seeds, N = 1000, runs of 7 rows; same
+// box, alternated, profiles/r06_groups_c3.txt) one 12-wave workgroup per CU runs 9.07-9.09 us against 8.50-8.54 us for three
+// 4-wave workgroups -- twelve waves now wait at the publishing barrier for the slowest of them instead of four.  Handles
+// start on 4-wave workgroups; va_problem_tune(VA_TUNE_WIDE, 1) puts one on the rule's width.
+constexpr bool EVAL4_WIDE_DEFAULT = false;
+
+// Row groups per workgroup of k_eval4, for `ntiles` row groups per seed at run length K.  A grid that is ONE resident
+// round of w 4-wave workgroups per CU runs in lockstep: the w workgroups of a CU stage, compute, publish and store
+// together, each with a publishing wave, an arrival and a dispatch slot of its own.  G of them as one workgroup keep
+// the waves per SIMD, the registers and the LDS of the CU as they are and leave one of each.  The largest G <= w for
+// which the busiest CU still owns no more row groups than before and the workgroup's LDS fits; 1 for any grid of more
+// than one round.
+inline int plan_eval4_groups(long batch, int ntiles, int K, int nb, const Geo4 &g4)
+{
+    const int w = eval4_per_cu(K, nb);
+    const long grid1 = batch * ntiles, rounds1 = (grid1 + EVAL4_CUS - 1) / EVAL4_CUS;      // (row groups on the busiest CU)
+    if (grid1 > (long)EVAL4_CUS * w) return 1;
+    for (int G = w; G > 1; --G) {
+        const long grid = batch * ((ntiles + G - 1) / G), rounds = (grid + EVAL4_CUS - 1) / EVAL4_CUS;
+        if (G * rounds <= rounds1 && sizeof(double) * (size_t)G * g4.NW * g4.WAVE <= 160 * 1024) return G;
+    }
+    return 1;
+}
+
 // wave-private column runs: T = 4 waves x RW runs x K rows, narrow even states that fill a wave, a column form
 inline bool plan_eval4(const va_problem_desc *d, const EvalForm &f, EvalPlan &p)
 {
@@ -190,6 +221,7 @@ inline bool plan_eval4(const va_problem_desc *d, const EvalForm &f, EvalPlan &p)
     p.g4 = g4;
     p.emode = 4; p.RY = 4 * RW; p.NT = 256; p.maxr = K; p.T = g4.T;
     p.ntiles = (N + p.T - 1) / p.T;
+    p.wg4 = plan_eval4_groups(d->batch, p.ntiles, K, f.nb, g4);
     return true;
 }
 
@@ -318,6 +350,7 @@ struct ModuleVariant {
     int ne = 0, ghost = 0, reach[4] = {0, 0, 0, 0};
     int has_linear = 0;                          // the flat kernel carries a dense linear part
     int n_colp_vectors = 0;                      // > 0: the instantiation is of the model's column-parameter form (RhsUserColP)
+    int nb = 0;                                  // kernel 4: neighbour columns of the column form (va_user_col_neighbours; 0: a module without it)
 
     static ModuleVariant decode(const int *v)
     {
@@ -334,6 +367,7 @@ struct ModuleVariant {
     {
         EvalForm f = flat_form();
         f.ne = (kernel == 4 || kernel == 5) ? ne : 0;
+        f.nb = kernel == 4 ? nb : 0;
         f.ghost = kernel == 3 ? ghost : 0;
         f.has_reach5 = kernel == 5;
         for (int k = 0; k < 4; ++k) f.reach5[k] = reach[k];

@@ -28,6 +28,7 @@
 #include "va_predict.h"
 #include "va_predict_tlm.h"
 #include "va_hvp.h"
+#include "va_eval4_builtin.h"
 
 namespace va {
 
@@ -60,39 +61,17 @@ static void eval3_d(const Dev &dv, EvalOp &op)
     else eval3_rhs<RHS, K, 0, 1024>(dv, op);
 }
 
-template <class RHS, int K, int DC, int WS>
-static void eval4_rhs(const Dev &dv, EvalOp &op)
-{
-    with_disc(dv.dm.disc, [&](auto disc) { eval4_op<RHS, decltype(disc)::value, K, DC, WS>(dv, op); });
-}
-
-// D = 20 (examples/Lorenz96_D20, BASELINE configs 1-3) is compiled with D as a constant; scalar RM /
-// RF0 with data at every model time (the same configs) run the variant without weight registers
-template <class RHS, int K>
-static void eval4_d(const Dev &dv, EvalOp &op)
-{
-    const bool sw = !dv.pp.rm_arr && !dv.pp.rf0_arr, ws = sw && dv.dm.nskip == 1;
-    if (dv.dm.D == 20) {
-        if (ws) eval4_rhs<RHS, K, 20, 1>(dv, op);
-        else if (sw) eval4_rhs<RHS, K, 20, 2>(dv, op);        // scalar weights, data at every nskip-th row
-        else eval4_rhs<RHS, K, 20, 0>(dv, op);
-    } else { if (ws) eval4_rhs<RHS, K, 0, 1>(dv, op); else eval4_rhs<RHS, K, 0, 0>(dv, op); }
-}
-
 // the built-in right-hand side's evaluation kernel: the one dv.dm.emode names
 static void eval_builtin(const Dev &dv, EvalOp &op)
 {
     if (dv.dm.emode == 5) eval5_builtin(dv, op);
     else if (dv.dm.emode == 4) {
-        switch (dv.dm.maxr) {
-        case 4: eval4_d<RhsL96s, 4>(dv, op); break;
-        case 5: eval4_d<RhsL96s, 5>(dv, op); break;
-        case 6: eval4_d<RhsL96s, 6>(dv, op); break;
-        case 7: eval4_d<RhsL96s, 7>(dv, op); break;
-        // runs of 12 rows at two workgroups per CU (D = 20, scalar weights, data at every row or every nskip-th: Simpson-Hermite at
-        // the C3 shape in ONE round of resident workgroups, see the chooser in va_capi.hip)
-        case 12: if (dv.dm.nskip == 1) eval4_rhs<RhsL96s, 12, 20, 1>(dv, op); else eval4_rhs<RhsL96s, 12, 20, 2>(dv, op); break;
-        default: eval4_d<RhsL96s, 8>(dv, op); break;
+        // (one translation unit per workgroup width: this one, va_eval4_g2.hip, va_eval4_g3.hip)
+        switch (eval4_groups(dv)) {
+        case 1: eval4_builtin<1>(dv, op); break;
+        case 2: eval4_builtin_g2(dv, op); break;
+        case 3: eval4_builtin_g3(dv, op); break;
+        default: op.err = hipErrorInvalidConfiguration; break;
         }
     } else if (dv.dm.emode == 3) {
         switch (dv.dm.maxr) {

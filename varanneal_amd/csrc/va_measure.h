@@ -11,7 +11,7 @@
 
 #ifdef VA_STAMPS
 #define VA_E4_STAMP_SETUP(dv, w)                                                                                                   \
-    unsigned long long *tl = reinterpret_cast<unsigned long long *>((dv).upp) + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 10; \
+    unsigned long long *tl = reinterpret_cast<unsigned long long *>((dv).upp) + ((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 10; \
     if ((threadIdx.x & 63) == 0) {                                                                                                 \
         tl[8] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);                                                     \
         tl[9] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned long long)(w);                  \

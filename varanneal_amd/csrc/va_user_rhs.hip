@@ -52,7 +52,7 @@ constexpr void (*user_eval_var)(const va::Dev &, va::EvalOp &) = nullptr;
 #elif VA_USER_VARIANT == 5
 constexpr auto user_eval_var = va::eval5_op<VA_USER_COLT, VA_USER_DISC, VA_USER_COLT::D>;
 #elif VA_USER_VARIANT == 4
-constexpr auto user_eval_var = va::eval4_op<VA_USER_COLT, VA_USER_DISC, VA_USER_K, VA_USER_COLT::D, VA_USER_W != 0>;
+constexpr auto user_eval_var = va::eval4_op_groups<VA_USER_COLT, VA_USER_DISC, VA_USER_K, VA_USER_COLT::D, VA_USER_W != 0>;      // (every workgroup width, Dev::wg4)
 #else
 constexpr auto user_eval_var = va::eval3_op<va::RhsUserG, VA_USER_DISC, VA_USER_K, va::RhsUserG::D, VA_USER_W>;     // (D compiled in, as the built-in's D = 200)
 #endif
@@ -114,6 +114,12 @@ void va_user_variant_info(int *out)
 #endif
 #endif
 }
+#if defined(VA_USER_VARIANT) && VA_USER_VARIANT == 4
+// Neighbour columns the carried k_eval4 instantiation's column form reads: with the run length they set the kernel's
+// registers, hence how many 4-wave workgroups a CU holds and which workgroup widths exist (eval4_wpc, va_eval4.h).
+// (An entry point of its own: va_user_variant_info's integers are counted by its callers.)
+int va_user_col_neighbours(void) { return VA_USER_COLT::NB; }
+#endif
 #if defined(VA_USER_COLP)
 // the column-parameter form's map: (shared scalars S, vectors V), then the global parameter index of each shared scalar
 // and of each vector entry (v, column i) at S + v D + i
