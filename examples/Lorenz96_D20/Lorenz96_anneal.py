@@ -7,9 +7,12 @@ the data file location.  Optional: --seeds B runs B random initial paths as one 
 --predict N holds the last N observations back from the fit, integrates the model N steps on
 from every rung's estimate (Annealer.predict) and prints the forecast's RMS error per rung;
 --spread N holds them back as well and prints the last rung's forecast with its +- 2 sigma band
-(Annealer.predict_spread) and the share of held-back observed values inside it at a few lead times.
+(Annealer.predict_spread) and the share of held-back observed values inside it at a few lead times;
+--lyapunov N prints, per seed, the leading Lyapunov exponent of the estimated model over N steps from the last rung's
+estimate, the forecast horizon 1 / lambda_1 in units of dt_model, the Kaplan-Yorke dimension (Annealer.lyapunov) and the
+largest conditional exponent with a gain on the measured columns (Annealer.sync_exponents).
 
-    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40] [--spread 40]
+    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40] [--spread 40] [--lyapunov 4000]
 """
 import argparse
 import os
@@ -39,6 +42,10 @@ def main():
     ap.add_argument("--spread", type=int, default=0, metavar="N",
                     help="hold the last N observations back and print the last rung's forecast +- 2 sigma (linearised spread "
                          "under the Laplace posterior: Annealer.predict_spread) and the share of them inside the band")
+    ap.add_argument("--lyapunov", type=int, default=0, metavar="N",
+                    help="print lambda_1, the horizon 1 / lambda_1 in steps of dt_model, the Kaplan-Yorke dimension and the largest "
+                         "conditional exponent at a few gains on the measured columns, over N model steps (a multiple of 4) from the "
+                         "last rung's estimate (Annealer.lyapunov, Annealer.sync_exponents)")
     ap.add_argument("--errorbars", action="store_true",
                     help="print the final k +- sigma per seed (Laplace approximation: Annealer.param_covariance)")
     ap.add_argument("--statebars", action="store_true",
@@ -129,6 +136,20 @@ def main():
                 inside = np.mean(np.abs(held_back[n] - mean[b, n, Lidx]) <= band)
                 print("seed %d   lead %3d steps   x_0 = %8.4f +- %.4f   inside the band: %3.0f %%"
                       % (b, n, mean[b, n, 0], 2.0 * std[b, n, 0], 100.0 * inside))
+
+    if args.lyapunov > 0:
+        # finite-time exponents of the estimated model (discrete RK4 map) from the estimate; the first tenth of the steps
+        # aligns the tangents and is left out of the averages
+        n_ly, gains = args.lyapunov, [0.0, 2.0, 5.0, 10.0]
+        ly = anneal1.lyapunov(n_ly, transient=n_ly // 10)
+        sy = anneal1.sync_exponents(n_ly, gains, transient=n_ly // 10)
+        lam1, hor, ky = np.ravel(ly["exponents"][..., 0]), np.ravel(ly["horizon"]), np.ravel(ly["kaplan_yorke"])
+        cond, crit = sy["exponents"][..., 0].reshape(-1, len(gains)), np.ravel(sy["critical_gain"])
+        print("\nLyapunov exponents of the estimated model over %d steps from the last rung's estimate" % n_ly)
+        for b in range(lam1.size):
+            print("seed %d   lambda_1 = %.4f   horizon = %.1f steps of dt_model   Kaplan-Yorke dimension = %.2f" % (b, lam1[b], hor[b] / dt_model, ky[b]))
+            print("         conditional lambda_1 with gain c on the %d measured columns: %s   smallest listed gain that synchronises: %s"
+                  % (len(Lidx), "  ".join("c=%g: %+.3f" % (c, v) for c, v in zip(gains, cond[b])), crit[b]))
 
     if args.errorbars:
         # inverse Hessian of the action as the package normalises it, at the last rung's minimisers; at large RF the

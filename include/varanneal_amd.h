@@ -285,6 +285,27 @@ int va_predict_tangent(va_handle h, const double *x0, const double *p, const dou
                        int32_t n_steps, int32_t substeps, int32_t every, const double *stim, double *out, double *dX,
                        double *var, double *cov);
 
+/* Lyapunov spectra of the handle's model (csrc/va_lyap.h): T trajectories from x0 with the parameters p, each with K <= D
+ * tangents carried by the tangent-linear model of the RK4 integrator (va_predict's steps, stage times and stimulus; the
+ * parameter tangent is zero) and re-orthonormalised together by a thin QR with positive diagonal after every qr_every model
+ * steps.  With gains g = coupling[t] >= 0 every tangent stage is J(x) v - g o v: the exponents are then the CONDITIONAL
+ * ones of a copy of the model driven through those columns.
+ *   x0 [T][D], p [T][NP]; Q0 [T][K][D] the starting tangents (rows), or NULL: the first K unit vectors;
+ *   coupling [T][D] or NULL; stim as va_predict's;  n_steps a multiple of qr_every, n_qr = n_steps / qr_every,
+ *   0 <= n_skip < n_qr: the QRs left out of the sums
+ *   logsum [T][K]: sum of log R_jj over the QRs n_skip .. n_qr - 1, in time order (the exponents are
+ *           logsum / ((n_qr - n_skip) qr_every dt_model));  x_end [T][D], Q_end [T][K][D]: where a following call starts
+ *           (at t0 + n_steps dt_model);  trace NULL or [T][n_qr][K]: every log R_jj;  status [T]: 0, or j + 1 of the first
+ *           R_jj that was zero or not finite -- that trajectory's logsum is then NaN, the call still returns VA_OK.
+ * Works on buffers of its own, chunked over trajectories, like va_predict_tangent; the handle's resident state is left alone.
+ * VA_EINVAL (before the device is touched): what va_predict rejects; K outside 1 .. D; n_steps not a multiple of qr_every;
+ * n_skip outside 0 .. n_qr - 1; a negative or non-finite gain.
+ * VA_EUNSUPPORTED (reason in va_last_error): network handles; modules with a split linear part; generated models without a
+ * flat form; D > 64 or (K + 1) D > 2048. */
+int va_lyapunov(va_handle h, const double *x0, const double *p, const double *Q0, const double *coupling, int32_t T, int32_t K,
+                double t0, int32_t n_steps, int32_t substeps, int32_t qr_every, int32_t n_skip, const double *stim,
+                double *logsum, double *x_end, double *Q_end, double *trace, int32_t *status);
+
 /* Sample exp(-A(X, p)) at one rf_scale: B Hamiltonian Monte Carlo chains, one per seed of the handle, on the device
  * (csrc/va_hmc.h).  An iteration draws a momentum p = z / sqrt(minv), runs n_leap leapfrog steps of size
  * eps_it = eps[b] (1 + jitter (2 u - 1)) -- n_leap evaluations by the handle's own evaluation kernel, an element-wise launch

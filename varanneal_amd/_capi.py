@@ -207,6 +207,8 @@ def lib():
     L.va_predict.argtypes = [h, c_dp, c_dp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp]
     L.va_predict_tangent.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32] + [c_dp] * 5
     L.va_predict_tangent.restype = C.c_int
+    L.va_lyapunov.argtypes = [h, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double] + [C.c_int32] * 4 + [c_dp] * 5 + [c_ip]
+    L.va_lyapunov.restype = C.c_int
     L.va_hess_vec.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, c_dp]
     L.va_hess_vec.restype = C.c_int
     L.va_blocktri_selinv.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [c_dp] * 9 + [c_ip]
@@ -250,7 +252,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_eval_grid", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_lyapunov", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -538,6 +540,56 @@ class Problem(object):
         ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
         check(self._L.va_predict_tangent(self._h, ptr(x0), ptr(p), ptr(V0), T, nvec, float(t0), n_steps, substeps, every, ptr(st),
                                          ptr(r["out"]), ptr(r.get("dx")), ptr(r.get("var")), ptr(r.get("cov"))))
+        return r
+
+    def lyapunov(self, x0, p, K, n_steps, t0=0.0, substeps=1, qr_every=1, n_skip=0, Q0=None, coupling=None, stim=None, trace=False):
+        """Lyapunov spectra of the model on the device (va_lyapunov; csrc/va_lyap.h): from the T states x0 (T, D) with the
+        full parameter vectors p (T, NP), K <= D tangents per trajectory carried by the tangent-linear RK4 map and
+        re-orthonormalised by a QR every qr_every model steps (n_steps a multiple of it).  Q0 (T, K, D) or (K, D): the
+        starting tangents (default: the first K unit vectors); coupling (T, D) or (D,): non-negative gains g, every tangent
+        stage then J(x) v - g o v (conditional exponents); n_skip: QRs left out of the sums.  Returns a dict: logsum (T, K),
+        the sums of log R_jj; exponents (T, K) = logsum / ((n_qr - n_skip) qr_every dt_model); x_end (T, D), Q_end (T, K, D);
+        status (T,), 0 or j + 1 of the first R_jj that was zero or not finite (that row of logsum is NaN; nothing raises);
+        and with trace=True trace (T, n_qr, K), every log R_jj."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("lyapunov: a network handle has no differential equation to integrate")
+        D, NP = self.desc.D, self.desc.NP
+        x0 = _f64(x0).reshape(-1, D)
+        T = x0.shape[0]
+        p = _f64(p).reshape(-1, NP) if NP else np.zeros((T, 0))
+        if p.shape[0] == 1 and T > 1:
+            p = np.ascontiguousarray(np.broadcast_to(p, (T, NP)))
+        if p.shape[0] != T:
+            raise ValueError("lyapunov: %d states but %d parameter vectors" % (T, p.shape[0]))
+        K, n_steps, substeps, qr_every, n_skip = int(K), int(n_steps), int(substeps), int(qr_every), int(n_skip)
+        if K < 1 or K > D:
+            raise ValueError("lyapunov: K=%d outside 1 .. D=%d" % (K, D))
+
+        def per_traj(arr, shape, what):
+            if arr is None:
+                return None
+            arr = _f64(arr)
+            if arr.shape == shape:
+                arr = np.broadcast_to(arr, (T,) + shape)
+            if arr.shape != (T,) + shape:
+                raise ValueError("lyapunov: %s must have shape %s or %s, got %s" % (what, (T,) + shape, shape, arr.shape))
+            return np.ascontiguousarray(arr)
+        Q0 = per_traj(Q0, (K, D), "Q0")
+        coupling = per_traj(coupling, (D,), "coupling")
+        st = None
+        if stim is not None:
+            st = _f64(stim).reshape(max(n_steps, 0) + 1, -1)
+            if st.shape[1] != self.desc.n_stim and self.desc.n_stim:
+                raise ValueError("lyapunov: the stimulus must have %d rows of %d column(s)" % (n_steps + 1, self.desc.n_stim))
+        n_qr = n_steps // qr_every if qr_every >= 1 and n_steps >= 1 else 0
+        r = dict(logsum=np.empty((T, K)), x_end=np.empty((T, D)), Q_end=np.empty((T, K, D)), status=np.zeros(T, dtype=np.int32))
+        if trace:
+            r["trace"] = np.empty((T, max(n_qr, 0), K))
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
+        check(self._L.va_lyapunov(self._h, ptr(x0), ptr(p), ptr(Q0), ptr(coupling), T, K, float(t0), n_steps, substeps, qr_every, n_skip,
+                                  ptr(st), ptr(r["logsum"]), ptr(r["x_end"]), ptr(r["Q_end"]), ptr(r.get("trace")),
+                                  r["status"].ctypes.data_as(c_ip)))
+        r["exponents"] = r["logsum"] / ((n_qr - n_skip) * qr_every * self.desc.dt_model)
         return r
 
     def hess_vec(self, XP, V, rf_scale, P=None, gauss_newton=False, tile_rows=0):

@@ -39,6 +39,7 @@
 #include "va_persist.h"
 #include "va_predict.h"
 #include "va_predict_tlm.h"
+#include "va_lyap.h"
 #include "va_hvp.h"
 #include "va_selinv.h"
 #include "va_hmc.h"
@@ -978,7 +979,8 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
     typedef int (*hvp_fn)(HvpTable *, int);
     if (hvp_fn hv = (hvp_fn)dlsym(u.dl, "va_user_hvp_table")) {
         const int hb = hv(&u.hvp, (int)sizeof(HvpTable));
-        if (hb != (int)sizeof(HvpTable) || u.hvp.hvp_bytes != (int)sizeof(HvpArgs) || u.hvp.tlm_bytes != (int)sizeof(PredictTlmArgs)) {
+        if (hb != (int)sizeof(HvpTable) || u.hvp.hvp_bytes != (int)sizeof(HvpArgs) || u.hvp.tlm_bytes != (int)sizeof(PredictTlmArgs)
+            || u.hvp.lyap_bytes != (int)sizeof(LyapArgs)) {
             dlclose(u.dl);
             return fail(VA_EINVAL, "%s was built against different headers (HvpTable %d vs %zu bytes): rebuild it", path, hb, sizeof(HvpTable));
         }
@@ -1315,6 +1317,79 @@ int va_predict_tangent(va_handle h, const double *x0, const double *p, const dou
         if (dX) HIPCHK(hipMemcpyAsync(dX + (size_t)t1 * nvec * row, dx_d, sizeof(double) * n * nvec * row, hipMemcpyDeviceToHost, h->stream));
         if (var) HIPCHK(hipMemcpyAsync(var + (size_t)t1 * row, var_d, sizeof(double) * n * row, hipMemcpyDeviceToHost, h->stream));
         if (cov) HIPCHK(hipMemcpyAsync(cov + (size_t)t1 * row * a.D, cov_d, sizeof(double) * n * row * a.D, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
+    }
+    HIPCHK(hipGetLastError());
+    return VA_OK;
+}
+
+// Lyapunov spectra (va_lyap.h): T trajectories with K tangents each, one workgroup per trajectory (or several trajectories
+// per wave), all QRs on the device; only the sums, the end points and (when asked for) the trace come back.  Chunked over
+// trajectories under a workspace limit; buffers of its own, like va_predict_tangent.
+int va_lyapunov(va_handle h, const double *x0, const double *p, const double *Q0, const double *coupling, int32_t T, int32_t K,
+                double t0, int32_t n_steps, int32_t substeps, int32_t qr_every, int32_t n_skip, const double *stim,
+                double *logsum, double *x_end, double *Q_end, double *trace, int32_t *status)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    if (!x0 || !p || !logsum || !x_end || !Q_end || !status) return fail(VA_EINVAL, "x0 / p / logsum / x_end / Q_end / status must not be NULL");
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "a network handle has no differential equation to integrate");
+    const Dims &dm = h->dv.dm;
+    char why[192];
+    if (!lyap_check_args(T, dm.D, K, n_steps, substeps, qr_every, n_skip, coupling, why, sizeof why)) return fail(VA_EINVAL, "va_lyapunov: %s", why);
+    const int nstim = h->dv.pp.nstim;
+    if (nstim > 0 && !stim) return fail(VA_EINVAL, "the model takes a stimulus of %d column(s): pass its %d rows from t0 on", nstim, n_steps + 1);
+    if (nstim == 0 && stim) return fail(VA_EINVAL, "the model takes no stimulus, but one was passed");
+    if (dm.lin) return fail(VA_EUNSUPPORTED, "va_lyapunov: the module's dense linear part was split off (LINEAR): build it with linear=False");
+    if (!h->rt.predict || !h->rt_hvp.predict_tlm)
+        return fail(VA_EUNSUPPORTED, "va_lyapunov: the model has no flat form f(x, i, p) to differentiate (more than %d parameters: "
+                                     "its module carries the column-parameter form only)", RHS_BIG_NP);
+    if ((int64_t)n_steps * substeps > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_steps x substeps does not fit 32-bit indexing");
+    LyapArgs a;
+    a.T = T; a.D = dm.D; a.NP = dm.NPt; a.K = K; a.nstim = nstim; a.n_steps = n_steps; a.substeps = substeps; a.qr_every = qr_every;
+    a.n_skip = n_skip; a.t0 = t0; a.dt = dm.dt;
+    const int n_qr = n_steps / qr_every;
+    const size_t per = lyap_traj_doubles(a.D, a.NP, K, n_qr, trace != nullptr);
+    const long C = lyap_chunk_trajs(per, T);
+    if (C < 1)
+        return fail(VA_EUNSUPPORTED, "va_lyapunov: one trajectory with a trace of %d QRs takes %.1f MiB of device workspace, the limit is "
+                                     "%zu MiB: a larger qr_every, or no trace", n_qr, (double)per * 8.0 / 1048576.0, LYAP_WORKSPACE_BYTES >> 20);
+    if (!plan_lyap(a.D, C, K, a.NP, nstim, a.geo)) return fail(VA_EUNSUPPORTED, "va_lyapunov: D=%d K=%d: %s", a.D, K, a.geo.why);
+    if (!h->rt_hvp.lyap) return fail(VA_EUNSUPPORTED, "va_lyapunov: the model's module carries no k_lyap for D=%d", a.D);
+    HIPCHK(hipSetDevice(h->device));
+    // one allocation: [stim | x0 | p | Q0 | coupling | logsum | x_end | Q_end | trace | status], all but the stimulus for one
+    // chunk of C trajectories
+    const size_t ns = (size_t)(n_steps + 1) * nstim, nx = (size_t)C * a.D, np = (size_t)C * a.NP, nq = (size_t)C * K * a.D, nq0 = Q0 ? nq : 0,
+                 ng = coupling ? nx : 0, nl = (size_t)C * K, ntr = trace ? (size_t)C * n_qr * K : 0;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (ns + nx + np + nq0 + ng + nl + nx + nq + ntr + (size_t)C + 1)));
+    struct Free { double *q; ~Free() { (void)hipFree(q); } } guard{buf};
+    double *st_d = buf, *x0_d = st_d + ns, *p_d = x0_d + nx, *q0_d = p_d + np, *g_d = q0_d + nq0, *ls_d = g_d + ng, *xe_d = ls_d + nl,
+           *qe_d = xe_d + nx, *tr_d = qe_d + nq;
+    int *stat_d = (int *)(tr_d + ntr);
+    if (ns) HIPCHK(hipMemcpyAsync(st_d, stim, sizeof(double) * ns, hipMemcpyHostToDevice, h->stream));
+    for (long t1 = 0; t1 < T; t1 += C) {
+        const long n = T - t1 < C ? T - t1 : C;
+        HIPCHK(hipMemcpyAsync(x0_d, x0 + (size_t)t1 * a.D, sizeof(double) * n * a.D, hipMemcpyHostToDevice, h->stream));
+        if (a.NP) HIPCHK(hipMemcpyAsync(p_d, p + (size_t)t1 * a.NP, sizeof(double) * n * a.NP, hipMemcpyHostToDevice, h->stream));
+        if (Q0) HIPCHK(hipMemcpyAsync(q0_d, Q0 + (size_t)t1 * K * a.D, sizeof(double) * n * K * a.D, hipMemcpyHostToDevice, h->stream));
+        if (coupling) HIPCHK(hipMemcpyAsync(g_d, coupling + (size_t)t1 * a.D, sizeof(double) * n * a.D, hipMemcpyHostToDevice, h->stream));
+        a.T = (int)n;
+        if (!plan_lyap(a.D, n, K, a.NP, nstim, a.geo)) {      // (the last chunk: the same plan on fewer workgroups)
+            (void)hipStreamSynchronize(h->stream);
+            return fail(VA_EUNSUPPORTED, "va_lyapunov: D=%d K=%d: %s", a.D, K, a.geo.why);
+        }
+        a.x0 = x0_d; a.p = p_d; a.Q0 = Q0 ? q0_d : nullptr; a.coupling = coupling ? g_d : nullptr; a.stim = ns ? st_d : nullptr;
+        a.logsum = ls_d; a.x_end = xe_d; a.Q_end = qe_d; a.trace = trace ? tr_d : nullptr; a.status = stat_d;
+        const hipError_t e = h->rt_hvp.lyap(a, h->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
+            return fail(VA_EHIP, "k_lyap launch: %s", hipGetErrorString(e));
+        }
+        HIPCHK(hipMemcpyAsync(logsum + (size_t)t1 * K, ls_d, sizeof(double) * n * K, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(x_end + (size_t)t1 * a.D, xe_d, sizeof(double) * n * a.D, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(Q_end + (size_t)t1 * K * a.D, qe_d, sizeof(double) * n * K * a.D, hipMemcpyDeviceToHost, h->stream));
+        if (trace) HIPCHK(hipMemcpyAsync(trace + (size_t)t1 * n_qr * K, tr_d, sizeof(double) * n * n_qr * K, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(status + t1, stat_d, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
     }
     HIPCHK(hipGetLastError());

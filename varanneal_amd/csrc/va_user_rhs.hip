@@ -3,7 +3,7 @@
 // varanneal_amd/codegen.py traces the user's `f(t, x, p)` (the callable of set_model,
 // varanneal/va_ode.py:56-67), differentiates it symbolically and writes a header that
 // defines `struct RhsUser` with f, J^T v and (df/dp)^T v.  This file instantiates the model's
-// kernels -- the flat-mapped tile kernel, the persistent ladder kernel, the RK4 predictor and its tangent-linear model, the Hessian-vector kernel and at most
+// kernels -- the flat-mapped tile kernel, the persistent ladder kernel, the RK4 predictor, its tangent-linear model and the Lyapunov-spectrum kernel, the Hessian-vector kernel and at most
 // ONE column-run kernel -- and exports the entry point va_user_rhs_table, which fills the table of
 // launchers (RhsTable, va_device.h) the host reaches them through, va_user_hvp_table for the launchers of the Hessian-vector
 // kernel and the tangent-linear predictor (HvpTable); two more functions return data
@@ -18,6 +18,7 @@
 #include "va_persist.h"
 #include "va_predict.h"
 #include "va_predict_tlm.h"
+#include "va_lyap.h"
 #include "va_hvp.h"
 
 #ifndef VA_USER_RHS_HEADER
@@ -68,12 +69,16 @@ template <class R> void fill_table(va::RhsTable &t)
     if constexpr (va::rhs_flat<R>::value) { t.eval = va::eval_flat_op<R>; t.predict = va::launch_predict<R, R::D>; }
     if constexpr (va::seed_kernel_exists<R>()) t.seed = va::seed_op<R>;
 }
-// the Hessian-vector kernel and the tangent-linear predictor: derivatives of the element-wise part only (a split-off linear
-// part would need products of its own), and only where a flat struct exists
+// the Hessian-vector kernel, the tangent-linear predictor and the Lyapunov-spectrum kernel: derivatives of the element-wise
+// part only (a split-off linear part would need products of its own), and only where a flat struct exists
 template <class R> void fill_hvp_table(va::HvpTable &t)
 {
-    t = va::HvpTable{(int)sizeof(va::HvpTable), (int)sizeof(va::HvpArgs), (int)sizeof(va::PredictTlmArgs), nullptr, nullptr};
-    if constexpr (va::rhs_flat<R>::value && !va::rhs_linear<R>::value) { t.hvp = va::launch_hvp<R>; t.predict_tlm = va::launch_predict_tlm<R, R::D>; }
+    t = va::HvpTable{(int)sizeof(va::HvpTable), (int)sizeof(va::HvpArgs), (int)sizeof(va::PredictTlmArgs), (int)sizeof(va::LyapArgs),
+                     nullptr, nullptr, nullptr};
+    if constexpr (va::rhs_flat<R>::value && !va::rhs_linear<R>::value) {
+        t.hvp = va::launch_hvp<R>; t.predict_tlm = va::launch_predict_tlm<R, R::D>;
+        if constexpr (R::D <= va::LYAP_MAX_D) t.lyap = va::launch_lyap<R, R::D>;
+    }
 }
 }  // namespace
 

@@ -60,6 +60,22 @@ def hmc_rescale_step(eps, accept_rate, target=0.8):
     return eps * np.exp2(np.where(d >= 0.0, d / (1.0 - target), d / target))
 
 
+def kaplan_yorke(exponents):
+    """Kaplan-Yorke dimension of a FULL spectrum in decreasing order (last axis): j + (l_1 + ... + l_j) / |l_{j+1}| with j the
+    largest count whose sum is not negative; 0 when even l_1 is negative, the number of exponents when nothing contracts,
+    NaN where an exponent is NaN."""
+    lam = np.asarray(exponents, dtype=np.float64)
+    K = lam.shape[-1]
+    cs = np.cumsum(lam, axis=-1)
+    j = np.sum(np.cumprod(cs >= 0.0, axis=-1), axis=-1)                          # leading run of non-negative partial sums
+    jj = np.minimum(j, K - 1)
+    head = np.where(j > 0, np.take_along_axis(cs, np.maximum(j - 1, 0)[..., None], axis=-1)[..., 0], 0.0)
+    nxt = np.take_along_axis(lam, jj[..., None], axis=-1)[..., 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ky = np.where(j >= K, float(K), j + head / np.abs(nxt))
+    return np.where(np.isnan(lam).any(axis=-1), np.nan, ky)[()]
+
+
 class Annealer(LadderAnnealer):
     _print_exit_message = True
 
@@ -623,6 +639,95 @@ class Annealer(LadderAnnealer):
             cov[bad] = np.nan
             out["cov"] = cov.reshape(lead + (n_out, D, D))
         return out
+
+    # ------------------------------------------------------------------ Lyapunov spectra of the fitted model
+    def _lyap_points(self, n_steps, k, beta, seeds, qr_every, transient, what):
+        """the selected points' (seed indices, rung indices, x0 (npts, D), p (npts, NP), K, n_skip)"""
+        if self._pb is None or not getattr(self, "initalized", False):
+            raise ValueError("%s() works after anneal() / anneal_init()" % what)
+        sb, kb = self._select(beta, seeds)
+        N, D, NP, NX = self.N_model, self.D, self.NP, self._NX
+        K = D if k is None else int(k)
+        n_steps, qr_every, transient = int(n_steps), int(qr_every), int(transient)
+        if K < 1 or K > D:
+            raise ValueError("%s: k=%d outside 1 .. D=%d" % (what, K, D))
+        if n_steps < 1 or qr_every < 1 or n_steps % qr_every:
+            raise ValueError("%s: n_steps=%d must be a positive multiple of qr_every=%d" % (what, n_steps, qr_every))
+        n_skip = -(-max(transient, 0) // qr_every)                                # whole QR intervals, rounded up
+        if n_skip >= n_steps // qr_every:
+            raise ValueError("%s: a transient of %d steps leaves none of the %d steps to average over" % (what, transient, n_steps))
+        rows = self._mp[sb][:, kb].reshape(len(sb) * len(kb), -1)
+        x0 = rows[:, (N - 1) * D:N * D]
+        p = rows[:, NX + (N - 1) * NP:NX + N * NP] if self._tdp else rows[:, NX:]
+        return sb, kb, x0, p, K, n_skip
+
+    def lyapunov(self, n_steps, k=None, beta=-1, seeds=None, substeps=1, qr_every=4, transient=0, coupling=None, stim=None):
+        """Lyapunov exponents of the ESTIMATED model at the estimates (after anneal()): from the LAST row of every selected
+        (seed, rung)'s minimising path with that rung's full parameter vector (the last row's with time-dependent
+        parameters), t0 = t_model[-1], the k leading exponents (None: all D) over n_steps steps of dt_model by Benettin's
+        method on the device (csrc/va_lyap.h): tangents carried by the tangent-linear RK4 map at dt_model / substeps and
+        re-orthonormalised every qr_every steps, all selected points in one call.
+          beta / seeds  as predict(); the default is the last rung
+          transient     model steps left out of the average while the tangents align (rounded up to whole QR intervals)
+          coupling      (D,) non-negative gains g: the CONDITIONAL exponents of v' = (J(x) - diag(g)) v (sync_exponents builds
+                        them from Lidx)
+          stim          (n_steps + 1, n_stim), as predict()
+        Returns a dict, leading axes (nbeta_sel,) or (B_sel, nbeta_sel):
+          exponents     (..., k)   in decreasing order as the QR orders them, per unit of model time
+          logsum        (..., k)   the sums of log R_jj they are formed from
+          horizon       (...)      1 / l_1: the time over which a small forecast error grows e-fold; inf where l_1 <= 0
+          kaplan_yorke  (...)      the Kaplan-Yorke dimension (only when the whole spectrum was asked for)
+          x_end (..., D), Q_end (..., k, D)   state and orthonormal tangents at the end (to continue from)
+          status        (...)      0, or j + 1 where the QR met a zero or non-finite R_jj: that point's exponents are NaN
+        These are finite-time exponents of the discrete RK4 map of the estimated model from the estimate -- not of the data."""
+        sb, kb, x0, p, K, n_skip = self._lyap_points(n_steps, k, beta, seeds, qr_every, transient, "lyapunov")
+        g = None
+        if coupling is not None:
+            g = np.asarray(coupling, dtype=np.float64)
+            if g.shape != (self.D,) or not np.all(np.isfinite(g)) or np.any(g < 0):
+                raise ValueError("lyapunov: coupling holds D = %d finite non-negative gains" % self.D)
+            g = np.ascontiguousarray(np.broadcast_to(g, x0.shape))
+        r = self._pb.lyapunov(x0, p, K, int(n_steps), t0=float(self.t_model[-1]), substeps=substeps, qr_every=int(qr_every),
+                              n_skip=n_skip, coupling=g, stim=stim)
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        lam = np.asarray(r["exponents"]).reshape(lead + (K,))
+        l1 = lam[..., 0]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            horizon = np.where(np.isnan(l1), np.nan, np.where(l1 > 0, 1.0 / l1, np.inf))
+        out = dict(exponents=lam, logsum=np.asarray(r["logsum"]).reshape(lead + (K,)), horizon=horizon,
+                   x_end=np.asarray(r["x_end"]).reshape(lead + (self.D,)), Q_end=np.asarray(r["Q_end"]).reshape(lead + (K, self.D)),
+                   status=np.asarray(r["status"]).reshape(lead))
+        if K == self.D:
+            out["kaplan_yorke"] = np.asarray(kaplan_yorke(lam)).reshape(lead)
+        return out
+
+    def sync_exponents(self, n_steps, gains, k=1, beta=-1, seeds=None, substeps=1, qr_every=4, transient=0, stim=None):
+        """Are the measured columns enough?  The k largest CONDITIONAL Lyapunov exponents of the estimated model coupled to
+        its own trajectory through the measured columns: gain c on the Lidx columns and 0 elsewhere, for every c in gains,
+        (selected points x gains) as one device batch (lyapunov() says how).  The synchronisation manifold y = x of
+        y' = f(y) + g o (x - y) is stable where the largest of them is negative.  Returns a dict:
+          exponents      (..., len(gains), k)
+          critical_gain  (...)  the smallest listed gain whose largest conditional exponent is negative; NaN if none is
+          gains          (len(gains),)
+          status         (..., len(gains))
+        The drive here is the model itself, started at the estimate; measured data drive the real thing."""
+        gains = np.atleast_1d(np.asarray(gains, dtype=np.float64))
+        if gains.ndim != 1 or gains.size < 1 or not np.all(np.isfinite(gains)) or np.any(gains < 0):
+            raise ValueError("sync_exponents: gains is a list of finite non-negative numbers")
+        sb, kb, x0, p, K, n_skip = self._lyap_points(n_steps, k, beta, seeds, qr_every, transient, "sync_exponents")
+        npts, G, D = x0.shape[0], gains.size, self.D
+        one = np.zeros((G, D))
+        one[:, np.asarray(self.Lidx, dtype=np.intp)] = gains[:, None]
+        r = self._pb.lyapunov(np.repeat(x0, G, axis=0), np.repeat(p, G, axis=0), K, int(n_steps), t0=float(self.t_model[-1]),
+                              substeps=substeps, qr_every=int(qr_every), n_skip=n_skip, coupling=np.tile(one, (npts, 1)), stim=stim)
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        lam = np.asarray(r["exponents"]).reshape(lead + (G, K))
+        neg = lam[..., 0] < 0.0
+        order = np.argsort(gains, kind="stable")
+        crit = np.full(lead, np.nan)
+        for gi in order[::-1]:                                                    # (the smallest such gain is written last)
+            crit = np.where(neg[..., gi], gains[gi], crit)
+        return dict(exponents=lam, critical_gain=crit, gains=gains, status=np.asarray(r["status"]).reshape(lead + (G,)))
 
     # ------------------------------------------------------------------ sampling exp(-A) at a rung
     def _hmc_mass(self, mass, k):
