@@ -934,7 +934,10 @@ def check_second_order(exprs, syms, D, NP, nstim, trials=2, rtol=1e-10):
                                     complex step of f; K_j and pgrad2 against SymPy derivatives of the components
                                     themselves (no shift involved)
     Returns the form checked ('switch' / 'uniform'), or None for a model with kinks (Piecewise, Abs, sign: no complex step) --
-    the only modules whose second-order functions go unchecked here; tests/test_hvp_cpu.py compiles the emitted text."""
+    the only modules whose second-order functions go unchecked here.  The selects such a module emits are held by the tests
+    instead, in both forms, against torch autograd of the same model text (tests/models/zoo.py kinked_small, kinked_stencil):
+    tests/test_hvp_cpu.py::test_generated_second_order_functions_against_autograd and ::test_kinked_model_through_the_phases
+    compile the emitted text on the host, tests/test_gpu_generated_tangents.py runs it in k_hvp, k_predict_tlm and k_lyap."""
     sp = _sympy()
     if any(e.has(sp.Piecewise, sp.Abs, sp.sign) for e in exprs):
         return None
