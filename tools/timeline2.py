@@ -47,6 +47,16 @@ for rep in range(4):
             m = key == v
             print("      %-3d n=%3d  start %.2f  landed %.2f  rows done median %.2f max %.2f  gather %.2f  barrier %.2f" % (
                 v, m.sum(), np.median(start[m]), np.median(landed[m]), np.median(rows[m]), rows[m].max(), np.median(gather[m]), np.median(barrier[m])))
+    # the head of the kernel, per wave: stamp 0 the wave starts, stamp 1 everything is requested (just before the wait for
+    # the wave's loads), stamp 2 they have landed.  Waves 1-3 only: the last-arriving publisher re-uses its slot 1 for the tail
+    issued = (us[:, 1:, 1] - us[:, 1:, 0]); waited = (us[:, 1:, 2] - us[:, 1:, 1])
+    print("   head, waves 1-3: issued (stamp 1 - 0) median %.2f p90 %.2f max %.2f; landed (stamp 2 - 1) median %.2f p90 %.2f max %.2f us" % (
+        np.median(issued), np.percentile(issued, 90), issued.max(), np.median(waited), np.percentile(waited, 90), waited.max()))
+    for v in np.unique(rank):
+        m = rank == v
+        print("      dispatch rank %d n=%3d  stamp 0 %.2f -> 1 %.2f -> 2 %.2f (medians);  issued median %.2f p90 %.2f  landed median %.2f p90 %.2f" % (
+            v, m.sum(), np.median(us[m, 1:, 0]), np.median(us[m, 1:, 1]), np.median(us[m, 1:, 2]),
+            np.median(issued[m]), np.percentile(issued[m], 90), np.median(waited[m]), np.percentile(waited[m], 90)))
     # per seed: its slowest workgroup against its median one, and where that workgroup sat
     worst = []
     for b in range(B):

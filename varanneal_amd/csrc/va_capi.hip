@@ -119,7 +119,8 @@ struct va_problem_s {
     int timed_chunk = 0;
     Dev timed_dv;                      // the device image the chunk was captured with (kernels take it by value):
     NnetDev timed_nn;                  //   the graph is replayed only while h->dv / h->nn still equal these bytes
-    double timed_armed_rf = -1.0;      // >= 0: every seed sits in PH_START at this rf_scale (S1 launches leave it so)
+    double timed_armed_rf = -1.0;      // >= 0: every seed sits in PH_START at this rf_scale (S1 launches leave it so);
+                                       //   what an S1 launch carries by value as Dev::s1_rf (run_eval)
     NnetDev nn;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -164,6 +165,10 @@ void run_eval(va_handle h, int epi)
 {
     if (epi != EPI_FINALIZE) h->timed_armed_rf = -1.0;      // (line-search launches move the seeds' states)
     h->dv.lsrun = epi == EPI_LS ? 1 : 0;       // (S1 evaluations put every seed in PH_START: no line-search points)
+    // An S1 launch takes phase and RF from its argument instead of the seeds' states -- while the handle KNOWS them: the
+    // caller armed every seed with this RF and nothing has moved a state since (each path that does resets timed_armed_rf).
+    // Every other launch kind reads the states.
+    h->dv.s1_rf = epi == EPI_FINALIZE ? h->timed_armed_rf : -1.0;
     EvalOp op{false, h->stream, hipSuccess};
     if (h->is_nnet ? !h->nn.small : !h->fold) {
         // (large grids: a workgroup that waits for its arrival to come back holds its LDS and wave
@@ -503,6 +508,7 @@ int begin_create(int device, void *stream, int lbfgs_m, int max_beta, int keep_p
     HIPCHK(hipSetDevice(device));
 
     h.reset(new va_problem_s());
+    h->dv.s1_rf = -1.0;
     h->device = device; h->keep_paths = keep_paths;
     if (stream) h->stream = (hipStream_t)stream;
     else {
@@ -1783,7 +1789,7 @@ int timed_prepare(va_handle h, double rf_scale, int iters)
     if (!h->tune_graph || iters < 8) { timed_graph_drop(h); return VA_OK; }
     const int chunk = timed_chunk_of(iters);
     // (the fields run_eval writes, as it will leave them: the comparison below must not see a stale line-search launch)
-    h->dv.lsrun = 0;
+    h->dv.lsrun = 0; h->dv.s1_rf = h->timed_armed_rf;
     h->dv.epi = (h->is_nnet ? !h->nn.small : !h->fold) ? EPI_NONE : EPI_FINALIZE;
     if (timed_graph_current(h, chunk)) return VA_OK;
     timed_graph_drop(h);

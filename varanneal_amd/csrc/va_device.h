@@ -82,6 +82,10 @@ struct Dev {
     const int *cpmap;
     double *evv;
     int cps, cpv, cpnsg;
+    // >= 0: this launch is an S1 evaluation -- the host has put EVERY seed in PH_START at this rf_scale (launch_init_states),
+    // so the kernel and its tail take phase and RF from here and read nothing of the seeds' states.  Negative: read them.
+    // Set by run_eval alone (va_capi.hip), from the RF the caller armed the seeds with; never inferred from lsrun.
+    double s1_rf;
 };
 
 // ------------------------------------------------------------------ one prepare-or-launch operation

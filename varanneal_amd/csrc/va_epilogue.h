@@ -227,7 +227,9 @@ __device__ __forceinline__ void eval_epilogue(const Dev &dv, int b, int lane, Se
         if (CP && dv.cpv) colp_tail(dv, b, lane, ev, 0);
         if (lane != 0) return;
         eval_tail<CP>(dv, b, 0, ev);
-        const double me = ev[EP_ME] * dm.cme, fe = ev[EP_FE] * dm.cfe * as_const(static_cast<const SeedHot *>(dv.st + b))->rf_scale;
+        // (an S1 launch carries its RF by value, Dev::s1_rf; otherwise the seed's own)
+        const double rf_scale = dv.s1_rf >= 0.0 ? dv.s1_rf : as_const(static_cast<const SeedHot *>(dv.st + b))->rf_scale;
+        const double me = ev[EP_ME] * dm.cme, fe = ev[EP_FE] * dm.cfe * rf_scale;
         dv.outA[b] = me + fe; dv.outme[b] = me; dv.outfe[b] = fe;
         return;
     }

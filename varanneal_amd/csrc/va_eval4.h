@@ -69,33 +69,112 @@ __global__ __launch_bounds__(256 * G, SUB > 1 ? 1 : eval4_wpc(K, RHS::NB)) void 
     double *xsw = smem + wave * g.WAVE, *r2w = xsw + SUB * g.XW, *strip = r2w + g.R2;
     const double *xg = dv.x + (size_t)b * dm.ld;
 
+    // The words of the kernel argument that the loads behind the images are made of, in registers BEFORE the first image
+    // is requested: no wait for an argument word stands between the images and the observations.
+    // (inputs only: an in-out operand does not compile in every instantiation)
+    const double *y_base = dv.pp.Y;
+    const int y_bytes = (int)(sizeof(double) * dm.N_data * dm.L), y_pitch = dm.L;
+    const unsigned long long obsmask = dm.obsmask;
+    const double s1_rf = dv.s1_rf;                            // launch-uniform: >= 0 an S1 evaluation (va_device.h)
+    asm volatile("" :: "s"(y_base), "s"(y_bytes), "s"(y_pitch), "s"(obsmask), "s"(s1_rf) : "memory");
+
     // stage x: every image in flight before anything else is waited for
 #pragma unroll
     for (int s = 0; s < SUB; ++s) tile4_dma<NI>(g, xg + (long)(n0w + s * RK - HL) * D, xsw + s * g.XW, lane);
 
+    // ... and right behind the images what depends on the kernel argument alone: the lane's observations (and weights)
+    const int a = lane / D, tx = lane - a * D;
+    const bool active = a < g.RW;
+    Tile4 t;
+    t.n0w = n0w; t.a = a; t.tx = tx; t.r0 = n0w + a * K;
+    t.l = obs_index(obsmask, tx);          // (Lidx is ascending on the device: va_problem_create sorts it)
+    t.wobs = t.l >= 0 ? dm.rm : 0.0;
+    t.xs = xsw; t.es = r2w;
+    t.gtg = dv.gt + (size_t)b * dm.ld;
+    T4Regs<K, NE> rg[SUB];
+    ColAcc<RHS> acc;
+    acc.clear();
+    if constexpr (WS == 2) {
+        // data at every nskip-th model row: the lane walks its rows once, counting data rows; rows without data read as 0
+        // (outside the buffer) and are masked out of the measurement terms by rg.has
+        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void *)y_base, 0, y_bytes, 0x00020000);
+        const bool obs = active && t.l >= 0;
+#pragma unroll
+        for (int s = 0; s < SUB; ++s) {
+            const int m0 = t.r0 + s * RK;
+            int nd = m0 / dm.nskip, rem = m0 - nd * dm.nskip;
+            unsigned has = 0u;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                typedef unsigned v2u __attribute__((ext_vector_type(2)));
+                const bool h = obs && rem == 0 && nd < dm.N_data && m0 + k < dm.N;
+                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(yr, h ? (nd * dm.L + t.l) * 8 : 0x7ffffff0, 0, 0);
+                rg[s].yv[k] = __hiloint2double((int)v.y, (int)v.x);
+                has |= h ? (1u << k) : 0u;
+                if (++rem == dm.nskip) { rem = 0; ++nd; }
+            }
+            rg[s].has = has;
+        }
+    } else if constexpr (W_SCALAR) {
+        // observations of the lane's own rows: one address per lane, the row stride rides in an SGPR;
+        // rows beyond the data and unobserved columns fall outside the buffer and read as 0
+        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void *)y_base, 0, y_bytes, 0x00020000);
+        const int voff = (active && t.l >= 0) ? (t.r0 * y_pitch + t.l) * 8 : 0x7ffffff0;
+#pragma unroll
+        for (int s = 0; s < SUB; ++s) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                typedef unsigned v2u __attribute__((ext_vector_type(2)));
+                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(yr, voff, (s * RK + k) * y_pitch * 8, 0);
+                rg[s].yv[k] = __hiloint2double((int)v.y, (int)v.x);
+            }
+        }
+    } else if (active) {
+#pragma unroll
+        for (int s = 0; s < SUB; ++s) {
+            Tile4 ts = t;
+            ts.r0 = t.r0 + s * RK;
+            tile4_obs<K, NE>(dm, dv.pp, ts, rg[s]);
+        }
+    }
+    // RF0 arrays: the lane's weights, requested with everything else (parked in the product arrays below: va_tile4.h)
+    static_assert(SUB == 1 || WS != 0, "sub-tiles are compiled for the scalar-weight variants only");
+    constexpr bool RFW = WS == 0 && tile4_rfw_in_lds<K, NE, HL, DC>();
+    double wq[SUB][K + HL];
+    if constexpr (RFW) {
+        if (dv.pp.rf0_arr && active) {
+#pragma unroll
+            for (int s = 0; s < SUB; ++s) {
+                Tile4 ts = t;
+                ts.r0 = t.r0 + s * RK;
+                tile4_rfw_load<K, HL>(dm, dv.pp, ts, D, wq[s]);
+            }
+        }
+    }
+
+    // The seed's state, requested behind everything that does not depend on it.  An S1 launch carries it in the kernel
+    // argument (Dev::s1_rf >= 0: every seed in PH_START at that RF, no line-search point): nothing of *st is read.  A
+    // line-search launch reads it per seed, and waits for it BEHIND the images and the observations; the d images, the early
+    // return and -- still -- the parameter loads below (Pfull, xg[ND + k], Pidx[k]: a loop of dependent scalar loads of
+    // run-time length) stand after that wait (profiles/r07_s1_head_c3.txt: what was moved, what was not).
     const auto *st = as_const(static_cast<const SeedHot *>(dv.st + b));
-    const int phase = st->phase;
-    if (phase != PH_START && phase != PH_LS) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // never end a wave under its own LDS loads
-        return;
+    int phase = PH_START;
+    double stp = 0.0, rf_scale = s1_rf;
+    if (!(s1_rf >= 0.0)) {
+        phase = st->phase; stp = st->stp; rf_scale = st->rf_scale;
+        if (phase != PH_START && phase != PH_LS) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // never end a wave under its own loads
+            return;
+        }
     }
     const int use_d = (phase == PH_LS);
-    const double stp = st->stp;
     const double *dg = dv.d + (size_t)b * dm.ld;
     if (use_d) {
 #pragma unroll
         for (int s = 0; s < SUB; ++s) tile4_dma<NI>(g, dg + (long)(n0w + s * RK - HL) * D, r2w + s * g.XW, lane);
     }
-
-    const int a = lane / D, tx = lane - a * D;
-    const bool active = a < g.RW;
-    Tile4 t;
-    t.n0w = n0w; t.a = a; t.tx = tx; t.r0 = n0w + a * K; t.use_d = use_d;
-    t.l = obs_index(dm.obsmask, tx);          // (Lidx is ascending on the device: va_problem_create sorts it)
-    t.wobs = t.l >= 0 ? dm.rm : 0.0;
-    t.c = 2.0 * st->rf_scale * dm.cfe;
-    t.xs = xsw; t.es = r2w;
-    t.gtg = dv.gt + (size_t)b * dm.ld;
+    t.use_d = use_d;
+    t.c = 2.0 * rf_scale * dm.cfe;
     if constexpr (NCV > 0) {
         // column-parameter form: the shared scalars (uniform) and the lane's own entries of the vectors, each from the
         // trial point when estimated (cpmap: global index, then index in p_est or -1)
@@ -132,69 +211,6 @@ __global__ __launch_bounds__(256 * G, SUB > 1 ? 1 : eval4_wpc(K, RHS::NB)) void 
             for (int j = 0; j < RHS::NP; ++j) t.p[j] = (dst == j) ? v : t.p[j];
         }
     }
-    T4Regs<K, NE> rg[SUB];
-    ColAcc<RHS> acc;
-    acc.clear();
-    if constexpr (WS == 2) {
-        // data at every nskip-th model row: the lane walks its rows once, counting data rows; rows without data read as 0
-        // (outside the buffer) and are masked out of the measurement terms by rg.has
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)dv.pp.Y, 0, (int)(sizeof(double) * dm.N_data * dm.L), 0x00020000);
-        const bool obs = active && t.l >= 0;
-#pragma unroll
-        for (int s = 0; s < SUB; ++s) {
-            const int m0 = t.r0 + s * RK;
-            int nd = m0 / dm.nskip, rem = m0 - nd * dm.nskip;
-            unsigned has = 0u;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                typedef unsigned v2u __attribute__((ext_vector_type(2)));
-                const bool h = obs && rem == 0 && nd < dm.N_data && m0 + k < dm.N;
-                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(yr, h ? (nd * dm.L + t.l) * 8 : 0x7ffffff0, 0, 0);
-                rg[s].yv[k] = __hiloint2double((int)v.y, (int)v.x);
-                has |= h ? (1u << k) : 0u;
-                if (++rem == dm.nskip) { rem = 0; ++nd; }
-            }
-            rg[s].has = has;
-        }
-    } else if constexpr (W_SCALAR) {
-        // observations of the lane's own rows: one address per lane, the row stride rides in an SGPR;
-        // rows beyond the data and unobserved columns fall outside the buffer and read as 0
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)dv.pp.Y, 0, (int)(sizeof(double) * dm.N_data * dm.L), 0x00020000);
-        const int voff = (active && t.l >= 0) ? (t.r0 * dm.L + t.l) * 8 : 0x7ffffff0;
-#pragma unroll
-        for (int s = 0; s < SUB; ++s) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                typedef unsigned v2u __attribute__((ext_vector_type(2)));
-                const v2u v = __builtin_amdgcn_raw_buffer_load_b64(yr, voff, (s * RK + k) * dm.L * 8, 0);
-                rg[s].yv[k] = __hiloint2double((int)v.y, (int)v.x);
-            }
-        }
-    } else if (active) {
-#pragma unroll
-        for (int s = 0; s < SUB; ++s) {
-            Tile4 ts = t;
-            ts.r0 = t.r0 + s * RK;
-            tile4_obs<K, NE>(dm, dv.pp, ts, rg[s]);
-        }
-    }
-    // RF0 arrays: the lane's weights, requested with everything else (parked in the product arrays below: va_tile4.h)
-    static_assert(SUB == 1 || WS != 0, "sub-tiles are compiled for the scalar-weight variants only");
-    constexpr bool RFW = WS == 0 && tile4_rfw_in_lds<K, NE, HL, DC>();
-    double wq[SUB][K + HL];
-    if constexpr (RFW) {
-        if (dv.pp.rf0_arr && active) {
-#pragma unroll
-            for (int s = 0; s < SUB; ++s) {
-                Tile4 ts = t;
-                ts.r0 = t.r0 + s * RK;
-                tile4_rfw_load<K, HL>(dm, dv.pp, ts, D, wq[s]);
-            }
-        }
-    }
-
     VA_E4_STAMP(1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the wave's images have landed
     __builtin_amdgcn_wave_barrier();

@@ -76,11 +76,15 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
     const int SLOTX = 4 * PR, SLOTY = 4 * YPMAX;              // doubles per ring slot
     const int sg = tile / NSG, grp = tile - sg * NSG;
 
+    // (an S1 launch carries phase and RF by value, Dev::s1_rf >= 0, and reads nothing of the seed's state: as k_eval4)
     const auto *st = as_const(static_cast<const SeedHot *>(dv.st + b));
-    const int phase = st->phase;
-    if (phase != PH_START && phase != PH_LS) return;
+    int phase = PH_START;
+    double stp = 0.0, rf_scale = dv.s1_rf;
+    if (!(dv.s1_rf >= 0.0)) {
+        phase = st->phase; stp = st->stp; rf_scale = st->rf_scale;
+        if (phase != PH_START && phase != PH_LS) return;
+    }
     const bool use_d = LSRUN && phase == PH_LS;
-    const double stp = st->stp;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -179,7 +183,7 @@ __global__ __launch_bounds__(64 * T5_WPG_MAX, 4) void k_eval5(const Dev dv)
         const double dt = dm.dt, hdt = 0.5 * dm.dt;
         // scalar weights: q = cw r, the measurement term c2 (x - y).  Weight arrays / data every nskip-th row (WARR):
         // the row's own weights come through the ring, q = cw w r and the term is c2 w (x - y), w = 0 where no data
-        const double cw = 2.0 * st->rf_scale * dm.cfe * (WARR ? 1.0 : dm.rf0);
+        const double cw = 2.0 * rf_scale * dm.cfe * (WARR ? 1.0 : dm.rf0);
         const double c2 = 2.0 * dm.cme * (WARR ? (obs ? 1.0 : 0.0) : wobs);
         const int nskip = WARR ? dm.nskip : 1;
 
