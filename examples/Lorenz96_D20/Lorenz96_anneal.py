@@ -12,7 +12,7 @@ from every rung's estimate (Annealer.predict) and prints the forecast's RMS erro
 estimate, the forecast horizon 1 / lambda_1 in units of dt_model, the Kaplan-Yorke dimension (Annealer.lyapunov) and the
 largest conditional exponent with a gain on the measured columns (Annealer.sync_exponents).
 
-    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40] [--spread 40] [--lyapunov 4000]
+    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40] [--spread 40] [--lyapunov 4000] [--shoot]
 """
 import argparse
 import os
@@ -46,6 +46,10 @@ def main():
                     help="print lambda_1, the horizon 1 / lambda_1 in steps of dt_model, the Kaplan-Yorke dimension and the largest "
                          "conditional exponent at a few gains on the measured columns, over N model steps (a multiple of 4) from the "
                          "last rung's estimate (Annealer.lyapunov, Annealer.sync_exponents)")
+    ap.add_argument("--shoot", action="store_true",
+                    help="refine the last rung to a model trajectory (strong-constraint fit of x(t_0) and k: Annealer.shoot) and "
+                         "print k, cost, path_distance and, with --predict N, the forecast error from its end beside the one "
+                         "from the annealed path's last row")
     ap.add_argument("--errorbars", action="store_true",
                     help="print the final k +- sigma per seed (Laplace approximation: Annealer.param_covariance)")
     ap.add_argument("--statebars", action="store_true",
@@ -150,6 +154,23 @@ def main():
             print("seed %d   lambda_1 = %.4f   horizon = %.1f steps of dt_model   Kaplan-Yorke dimension = %.2f" % (b, lam1[b], hor[b] / dt_model, ky[b]))
             print("         conditional lambda_1 with gain c on the %d measured columns: %s   smallest listed gain that synchronises: %s"
                   % (len(Lidx), "  ".join("c=%g: %+.3f" % (c, v) for c, v in zip(gains, cond[b])), crit[b]))
+
+    if args.shoot:
+        # the RF -> infinity limit done exactly: a model trajectory fitted to the data window from the last rung's first
+        # row and parameters; its end is on a model orbit, the annealed path's last row carries that rung's model error
+        sh = anneal1.shoot(beta=-1)
+        ks, cost, dist = np.ravel(sh["params"][..., 0]), np.ravel(sh["cost"]), np.ravel(sh["path_distance"])
+        ends, pars = sh["path"].reshape(-1, N_model, D)[:, -1], sh["params"].reshape(-1, 1)
+        print("\nmodel trajectory fitted to the data window from the last rung (Annealer.shoot)")
+        for b in range(ks.size):
+            line = "seed %d   k = %.5f   cost = %.6g   path_distance = %.4g" % (b, ks[b], cost[b], dist[b])
+            if held_back is not None:
+                n_fc = len(held_back) - 1
+                fc = anneal1._pb.predict(ends[b], pars[b], n_fc, t0=float(anneal1.t_model[-1]))[0]
+                e_sh = np.sqrt(np.mean((fc[1:, Lidx] - held_back[1:]) ** 2))
+                e_an = np.ravel(anneal1.prediction_error(held_back)[..., -1])[b]
+                line += "   forecast RMS error from path[-1]: %.4f, from the annealed path's last row: %.4f" % (e_sh, e_an)
+            print(line)
 
     if args.errorbars:
         # inverse Hessian of the action as the package normalises it, at the last rung's minimisers; at large RF the

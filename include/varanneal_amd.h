@@ -285,6 +285,28 @@ int va_predict_tangent(va_handle h, const double *x0, const double *p, const dou
                        int32_t n_steps, int32_t substeps, int32_t every, const double *stim, double *out, double *dX,
                        double *var, double *cov);
 
+/* Adjoint of the forecast (csrc/va_predict_adj.h): va_predict's trajectories and, for ncot cotangent sets per trajectory, the
+ * transpose of the derivative of the DISCRETE RK4 map that va_predict_tangent applies (not a discretisation of the continuous
+ * adjoint equation): gx0 = (d out / d x0)^T G and gp = (d out / d p_est)^T G, one backward sweep per set.  The nominal is
+ * integrated forward with checkpoints of every RK4 step (n_steps * substeps * D doubles per trajectory and workgroup that
+ * carries it, in device memory), then the steps are walked backward.
+ *   x0, p, T, t0, n_steps, substeps, every, stim as in va_predict
+ *   exactly one of G and Y:
+ *   G [T*ncot*n_out*D] cotangent mode: the cotangents of the output rows
+ *   Y [T*n_out*L], or [n_out*L] with y_shared != 0: misfit mode, ncot = 1: observations of the handle's Lidx columns (in the
+ *        order the handle was created with) at the output rows; weights [L].  The cotangents are 2 w_l (x_l - y_l) and
+ *        cost [T] = sum over rows and columns of w_l (x_l - y_l)^2 (per column in row order, then over the columns in order)
+ *   out [T*n_out*D] the nominal trajectory; gx0 [T*ncot*D]; gp [T*ncot*NPest], the estimated parameters in Pidx order
+ * All arrays HOST.  No atomics anywhere: the same bits on every call.  The handle's bounds are ignored; its resident paths,
+ * seed states and captured graphs are left alone.
+ * VA_EINVAL: what va_predict rejects; both or neither of G and Y; ncot < 1; misfit mode with ncot != 1, no weights or no cost.
+ * VA_EUNSUPPORTED (reason in va_last_error): network handles; D > 1024; generated models without a flat form (more than
+ * 128 parameters); modules with a split linear part; parameters and partials past 64 KiB of LDS; one trajectory's
+ * checkpoints and cotangents past the workspace limit. */
+int va_predict_adjoint(va_handle h, const double *x0, const double *p, const double *G, const double *Y, const double *weights,
+                       int32_t y_shared, int32_t T, int32_t ncot, double t0, int32_t n_steps, int32_t substeps, int32_t every,
+                       const double *stim, double *out, double *gx0, double *gp, double *cost);
+
 /* Lyapunov spectra of the handle's model (csrc/va_lyap.h): T trajectories from x0 with the parameters p, each with K <= D
  * tangents carried by the tangent-linear model of the RK4 integrator (va_predict's steps, stage times and stimulus; the
  * parameter tangent is zero) and re-orthonormalised together by a thin QR with positive diagonal after every qr_every model

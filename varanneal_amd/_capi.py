@@ -207,6 +207,9 @@ def lib():
     L.va_predict.argtypes = [h, c_dp, c_dp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp]
     L.va_predict_tangent.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32] + [c_dp] * 5
     L.va_predict_tangent.restype = C.c_int
+    L.va_predict_adjoint.argtypes = [h, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                     C.c_int32] + [c_dp] * 5
+    L.va_predict_adjoint.restype = C.c_int
     L.va_lyapunov.argtypes = [h, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double] + [C.c_int32] * 4 + [c_dp] * 5 + [c_ip]
     L.va_lyapunov.restype = C.c_int
     L.va_hess_vec.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, c_dp]
@@ -252,7 +255,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_eval_grid", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_lyapunov", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_predict_adjoint", "va_lyapunov", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -540,6 +543,61 @@ class Problem(object):
         ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
         check(self._L.va_predict_tangent(self._h, ptr(x0), ptr(p), ptr(V0), T, nvec, float(t0), n_steps, substeps, every, ptr(st),
                                          ptr(r["out"]), ptr(r.get("dx")), ptr(r.get("var")), ptr(r.get("cov"))))
+        return r
+
+    def predict_adjoint(self, x0, p, n_steps, G=None, Y=None, weights=None, t0=0.0, substeps=1, every=1, stim=None):
+        """predict() and one backward sweep per cotangent set: the transpose of the derivative of the discrete RK4 map that
+        predict_tangent applies, on the device (va_predict_adjoint; csrc/va_predict_adj.h).  Pass exactly one of
+        G (T, ncot, n_out, D), or (ncot, n_out, D) for one trajectory: the cotangents of the output rows (cotangent mode), and
+        Y (T, n_out, L) or (n_out, L), shared by the trajectories: observations of the handle's Lidx columns at the output rows,
+        with weights (L,) (misfit mode: the cotangents are 2 w (x - y)).  Returns a dict: out (T, n_out, D), the nominal
+        trajectories; gx0 (T, ncot, D) and gp (T, ncot, NPest), the gradients with respect to x0 and the estimated
+        parameters; in misfit mode cost (T,) = sum w (x - y)^2.  The handle's bounds are ignored."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("predict_adjoint: a network handle has no differential equation to integrate")
+        if (G is None) == (Y is None):
+            raise ValueError("predict_adjoint: pass exactly one of G (cotangent mode) and Y (misfit mode)")
+        D, NP, NPe = self.desc.D, self.desc.NP, self.NPest
+        x0 = _f64(x0).reshape(-1, D)
+        T = x0.shape[0]
+        p = _f64(p).reshape(-1, NP) if NP else np.zeros((T, 0))
+        if p.shape[0] == 1 and T > 1:
+            p = np.ascontiguousarray(np.broadcast_to(p, (T, NP)))
+        if p.shape[0] != T:
+            raise ValueError("predict_adjoint: %d states but %d parameter vectors" % (T, p.shape[0]))
+        n_steps, substeps, every = int(n_steps), int(substeps), int(every)
+        n_out = n_steps // every + 1 if every >= 1 and n_steps >= 1 else 1
+        st = None
+        if stim is not None:
+            st = _f64(stim).reshape(max(n_steps, 0) + 1, -1)
+            if st.shape[1] != self.desc.n_stim and self.desc.n_stim:
+                raise ValueError("predict_adjoint: the stimulus must have %d rows of %d column(s)" % (n_steps + 1, self.desc.n_stim))
+        w, shared, ncot = None, 0, 1
+        if G is not None:
+            G = _f64(G)
+            if G.size == 0 or G.shape[-2:] != (n_out, D) or G.size % (T * n_out * D) or G.ndim not in (3, 4) or (G.ndim == 4 and G.shape[0] != T):
+                raise ValueError("predict_adjoint: G must have shape (%d, ncot, n_out = %d, D = %d), got %s" % (T, n_out, D, G.shape))
+            G = G.reshape(T, -1, n_out, D)
+            ncot = G.shape[1]
+        else:
+            Ld = self.desc.L
+            Y = _f64(Y)
+            if Y.shape not in ((n_out, Ld), (T, n_out, Ld)):
+                raise ValueError("predict_adjoint: Y must have shape (n_out = %d, L = %d) or (%d, %d, %d), got %s" % (n_out, Ld, T, n_out, Ld, Y.shape))
+            shared = 1 if Y.ndim == 2 else 0
+            if weights is None:
+                raise ValueError("predict_adjoint: misfit mode takes weights of shape (L = %d,)" % Ld)
+            w = _f64(weights)
+            if w.shape != (Ld,):
+                raise ValueError("predict_adjoint: weights must have shape (L = %d,), got %s" % (Ld, w.shape))
+        if G is not None and weights is not None:
+            raise ValueError("predict_adjoint: weights belong to misfit mode (Y)")
+        r = dict(out=np.empty((T, n_out, D)), gx0=np.empty((T, ncot, D)), gp=np.empty((T, ncot, NPe)))
+        if Y is not None:
+            r["cost"] = np.empty(T)
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
+        check(self._L.va_predict_adjoint(self._h, ptr(x0), ptr(p), ptr(G), ptr(Y), ptr(w), shared, T, ncot, float(t0), n_steps, substeps,
+                                         every, ptr(st), ptr(r["out"]), ptr(r["gx0"]), ptr(r["gp"]), ptr(r.get("cost"))))
         return r
 
     def lyapunov(self, x0, p, K, n_steps, t0=0.0, substeps=1, qr_every=1, n_skip=0, Q0=None, coupling=None, stim=None, trace=False):

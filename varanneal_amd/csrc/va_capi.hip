@@ -39,6 +39,7 @@
 #include "va_persist.h"
 #include "va_predict.h"
 #include "va_predict_tlm.h"
+#include "va_predict_adj.h"
 #include "va_lyap.h"
 #include "va_hvp.h"
 #include "va_selinv.h"
@@ -130,6 +131,7 @@ struct va_problem_s {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int64_t n_eval_launch = 0, n_seed_evals = 0, n_seed_evals_direct = 0, n_cycles = 0;
     int last_nbeta = 0;
+    std::vector<int> lidx_user;        // the observed columns in the caller's order (the device keeps them sorted): va_predict_adjoint's Y
 
     template <class T> int alloc(T **p, size_t n, bool zero = true)
     {
@@ -756,6 +758,7 @@ int upload_problem_data(va_handle h, const va_problem_desc *d, const UserRhs *us
     for (int l = 0; l < dm.L; ++l) perm[l] = l;
     if (d->rm_kind != 2) std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return d->Lidx[a] < d->Lidx[b]; });
     for (int l = 0; l < dm.L; ++l) lidx_sorted[l] = d->Lidx[perm[l]];
+    h->lidx_user.assign(d->Lidx, d->Lidx + dm.L);
     o.Ys.assign((size_t)dm.N_data * LY, 0.0);
     for (int n = 0; n < dm.N_data; ++n)
         for (int l = 0; l < dm.L; ++l) o.Ys[(size_t)n * LY + l] = d->Y[(size_t)n * dm.L + perm[l]];
@@ -986,7 +989,7 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
     if (hvp_fn hv = (hvp_fn)dlsym(u.dl, "va_user_hvp_table")) {
         const int hb = hv(&u.hvp, (int)sizeof(HvpTable));
         if (hb != (int)sizeof(HvpTable) || u.hvp.hvp_bytes != (int)sizeof(HvpArgs) || u.hvp.tlm_bytes != (int)sizeof(PredictTlmArgs)
-            || u.hvp.lyap_bytes != (int)sizeof(LyapArgs)) {
+            || u.hvp.lyap_bytes != (int)sizeof(LyapArgs) || u.hvp.adj_bytes != (int)sizeof(PredictAdjArgs)) {
             dlclose(u.dl);
             return fail(VA_EINVAL, "%s was built against different headers (HvpTable %d vs %zu bytes): rebuild it", path, hb, sizeof(HvpTable));
         }
@@ -1323,6 +1326,92 @@ int va_predict_tangent(va_handle h, const double *x0, const double *p, const dou
         if (dX) HIPCHK(hipMemcpyAsync(dX + (size_t)t1 * nvec * row, dx_d, sizeof(double) * n * nvec * row, hipMemcpyDeviceToHost, h->stream));
         if (var) HIPCHK(hipMemcpyAsync(var + (size_t)t1 * row, var_d, sizeof(double) * n * row, hipMemcpyDeviceToHost, h->stream));
         if (cov) HIPCHK(hipMemcpyAsync(cov + (size_t)t1 * row * a.D, cov_d, sizeof(double) * n * row * a.D, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
+    }
+    HIPCHK(hipGetLastError());
+    return VA_OK;
+}
+
+// Adjoint of the forecast (va_predict_adj.h): the nominal trajectories of va_predict and, for ncot cotangent sets each, the
+// transpose of the derivative of the discrete RK4 map va_predict_tangent applies -- gx0 = (d out / d x0)^T G and
+// gp = (d out / d p_est)^T G.  Cotangent mode: the caller's G.  Misfit mode (G NULL, ncot = 1): the cotangents are
+// 2 w_l (x_l - y_l) at the handle's observed columns and cost = sum w_l (x_l - y_l)^2 comes back with them.  Chunked over
+// trajectories: the buffers of a chunk, checkpoints included, stay under 1 GiB.  Works on buffers of its own, like va_predict.
+int va_predict_adjoint(va_handle h, const double *x0, const double *p, const double *G, const double *Y, const double *weights,
+                       int32_t y_shared, int32_t T, int32_t ncot, double t0, int32_t n_steps, int32_t substeps, int32_t every,
+                       const double *stim, double *out, double *gx0, double *gp, double *cost)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    if (!x0 || !p || !out || !gx0) return fail(VA_EINVAL, "x0 / p / out / gx0 must not be NULL");
+    if (T < 1 || n_steps < 1 || substeps < 1 || every < 1)
+        return fail(VA_EINVAL, "T, n_steps, substeps and every must be at least 1 (T=%d n_steps=%d substeps=%d every=%d)", T, n_steps, substeps, every);
+    if ((G != nullptr) == (Y != nullptr)) return fail(VA_EINVAL, "va_predict_adjoint: pass exactly one of G (cotangent mode) and Y (misfit mode)");
+    if (ncot < 1) return fail(VA_EINVAL, "ncot must be at least 1 (ncot=%d)", ncot);
+    if (Y && (ncot != 1 || !weights || !cost)) return fail(VA_EINVAL, "va_predict_adjoint: misfit mode takes ncot = 1, weights and cost (ncot=%d)", ncot);
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "a network handle has no differential equation to integrate");
+    const Dims &dm = h->dv.dm;
+    const int nstim = h->dv.pp.nstim;
+    if (dm.NPest > 0 && !gp) return fail(VA_EINVAL, "gp must not be NULL (%d estimated parameter(s))", dm.NPest);
+    if (nstim > 0 && !stim) return fail(VA_EINVAL, "the model takes a stimulus of %d column(s): pass its %d rows from t0 on", nstim, n_steps + 1);
+    if (nstim == 0 && stim) return fail(VA_EINVAL, "the model takes no stimulus, but one was passed");
+    if (dm.lin) return fail(VA_EUNSUPPORTED, "va_predict_adjoint: the module's dense linear part was split off (LINEAR): build it with linear=False");
+    if (!h->rt.predict || !h->rt_hvp.predict_adj)
+        return fail(VA_EUNSUPPORTED, "va_predict_adjoint: the model has no flat form f(x, i, p) to differentiate (more than %d parameters: "
+                                     "its module carries the column-parameter form only)", RHS_BIG_NP);
+    if ((int64_t)n_steps * substeps > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_steps x substeps does not fit 32-bit indexing");
+    PredictAdjArgs a;
+    a.T = T; a.D = dm.D; a.NP = dm.NPt; a.NPest = dm.NPest; a.ncot = ncot; a.L = Y ? dm.L : 0; a.nstim = nstim; a.n_steps = n_steps;
+    a.substeps = substeps; a.every = every; a.n_out = n_steps / every + 1; a.t0 = t0; a.dt = dm.dt; a.Pidx = h->dv.pp.Pidx;
+    const long long Q = (long long)n_steps * substeps;
+    const size_t row = (size_t)a.n_out * a.D, yrow = (size_t)a.n_out * a.L;
+    if (!plan_predict_adj(a.D, T, ncot, a.NP, nstim, a.geo)) return fail(VA_EUNSUPPORTED, "va_predict_adjoint: D=%d ncot=%d: %s", a.D, ncot, a.geo.why);
+    const size_t per = predict_adj_traj_doubles(a.D, a.NP, a.NPest, ncot, a.n_out, Q, a.geo.nchunks, G ? ncot * row : (y_shared ? 0 : yrow));
+    const size_t spare = (size_t)a.geo.RW * a.geo.nchunks * (size_t)Q * a.D + (size_t)(n_steps + 1) * nstim + yrow + 2 * (size_t)a.L + 8;
+    const long C = predict_adj_chunk_trajs(per, spare, T);
+    if (C < 1)
+        return fail(VA_EUNSUPPORTED, "va_predict_adjoint: one trajectory with %d cotangent set(s), %d output row(s) and %lld checkpoints takes "
+                                     "%.1f MiB of device workspace, the limit is %zu MiB: fewer steps or sets, or a larger `every`", ncot,
+                    a.n_out, Q * a.geo.nchunks, (double)(per + spare) * 8.0 / 1048576.0, PREDICT_ADJ_WORKSPACE_BYTES >> 20);
+    if (!plan_predict_adj(a.D, C, ncot, a.NP, nstim, a.geo)) return fail(VA_EUNSUPPORTED, "va_predict_adjoint: D=%d ncot=%d: %s", a.D, ncot, a.geo.why);
+    HIPCHK(hipSetDevice(h->device));
+    // one allocation: [stim | w | Lidx | x0 | p | G or Y | out | gx0 | gp | cost | checkpoints], all but the first three (and a
+    // shared Y) for one chunk of C trajectories
+    const size_t ns = (size_t)(n_steps + 1) * nstim, nwt = a.L, nli = ((size_t)a.L + 1) / 2, nx = (size_t)C * a.D, np = (size_t)C * a.NP,
+                 ncg = G ? (size_t)C * ncot * row : (y_shared ? yrow : (size_t)C * yrow), no = C * row, ngx = (size_t)C * ncot * a.D,
+                 ngp = (size_t)C * ncot * a.NPest, nc = Y ? (size_t)C : 0, nck = predict_adj_ckpt_doubles(a.geo, a.D, Q);
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (ns + nwt + nli + nx + np + ncg + no + ngx + ngp + nc + nck + 1)));
+    struct Free { double *q; ~Free() { (void)hipFree(q); } } guard{buf};
+    double *st_d = buf, *w_d = st_d + ns, *li_d = w_d + nwt, *x0_d = li_d + nli, *p_d = x0_d + nx, *cg_d = p_d + np, *out_d = cg_d + ncg,
+           *gx_d = out_d + no, *gp_d = gx_d + ngx, *c_d = gp_d + ngp, *ck_d = c_d + nc;
+    if (ns) HIPCHK(hipMemcpyAsync(st_d, stim, sizeof(double) * ns, hipMemcpyHostToDevice, h->stream));
+    if (a.L) {
+        HIPCHK(hipMemcpyAsync(w_d, weights, sizeof(double) * a.L, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(li_d, h->lidx_user.data(), sizeof(int) * a.L, hipMemcpyHostToDevice, h->stream));
+        if (y_shared) HIPCHK(hipMemcpyAsync(cg_d, Y, sizeof(double) * yrow, hipMemcpyHostToDevice, h->stream));
+    }
+    for (long t1 = 0; t1 < T; t1 += C) {
+        const long n = T - t1 < C ? T - t1 : C;
+        HIPCHK(hipMemcpyAsync(x0_d, x0 + (size_t)t1 * a.D, sizeof(double) * n * a.D, hipMemcpyHostToDevice, h->stream));
+        if (a.NP) HIPCHK(hipMemcpyAsync(p_d, p + (size_t)t1 * a.NP, sizeof(double) * n * a.NP, hipMemcpyHostToDevice, h->stream));
+        if (G) HIPCHK(hipMemcpyAsync(cg_d, G + (size_t)t1 * ncot * row, sizeof(double) * n * ncot * row, hipMemcpyHostToDevice, h->stream));
+        else if (!y_shared && yrow) HIPCHK(hipMemcpyAsync(cg_d, Y + (size_t)t1 * yrow, sizeof(double) * n * yrow, hipMemcpyHostToDevice, h->stream));
+        a.T = (int)n;
+        if (!plan_predict_adj(a.D, n, ncot, a.NP, nstim, a.geo) || predict_adj_ckpt_doubles(a.geo, a.D, Q) > nck) {      // (the last chunk: the same plan on fewer workgroups)
+            (void)hipStreamSynchronize(h->stream);
+            return fail(VA_EUNSUPPORTED, "va_predict_adjoint: D=%d ncot=%d: %s", a.D, ncot, a.geo.why);
+        }
+        a.x0 = x0_d; a.p = p_d; a.G = G ? cg_d : nullptr; a.Y = Y ? cg_d : nullptr; a.w = w_d; a.Lidx = (const int *)li_d;
+        a.y_stride = y_shared ? 0 : yrow; a.stim = ns ? st_d : nullptr; a.out = out_d; a.gx0 = gx_d; a.gp = gp_d; a.cost = c_d; a.ckpt = ck_d;
+        const hipError_t e = h->rt_hvp.predict_adj(a, h->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
+            return fail(VA_EHIP, "k_predict_adj launch: %s", hipGetErrorString(e));
+        }
+        HIPCHK(hipMemcpyAsync(out + (size_t)t1 * row, out_d, sizeof(double) * n * row, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(gx0 + (size_t)t1 * ncot * a.D, gx_d, sizeof(double) * n * ncot * a.D, hipMemcpyDeviceToHost, h->stream));
+        if (a.NPest) HIPCHK(hipMemcpyAsync(gp + (size_t)t1 * ncot * a.NPest, gp_d, sizeof(double) * n * ncot * a.NPest, hipMemcpyDeviceToHost, h->stream));
+        if (Y) HIPCHK(hipMemcpyAsync(cost + t1, c_d, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
     }
     HIPCHK(hipGetLastError());

@@ -152,11 +152,14 @@ void builtin_rhs_table(RhsTable &t);
 // (va_user_rhs.hip); a module without that entry point has no such kernels.
 struct PredictTlmArgs;
 struct LyapArgs;
+struct PredictAdjArgs;
 struct HvpTable {
     int bytes, hvp_bytes, tlm_bytes, lyap_bytes;      // sizeof(HvpTable), sizeof(HvpArgs), sizeof(PredictTlmArgs), sizeof(LyapArgs)
+    int adj_bytes;                                    // sizeof(PredictAdjArgs)
     hipError_t (*hvp)(const HvpArgs &, size_t lds_bytes, hipStream_t);      // or NULL
     hipError_t (*predict_tlm)(const PredictTlmArgs &, hipStream_t);         // or NULL
     hipError_t (*lyap)(const LyapArgs &, hipStream_t);                      // or NULL
+    hipError_t (*predict_adj)(const PredictAdjArgs &, hipStream_t);         // the adjoint predictor (va_predict_adj.h), or NULL
 };
 void builtin_hvp_table(HvpTable &t);
 

@@ -27,6 +27,7 @@
 #include "va_persist.h"
 #include "va_predict.h"
 #include "va_predict_tlm.h"
+#include "va_predict_adj.h"
 #include "va_lyap.h"
 #include "va_hvp.h"
 #include "va_eval4_builtin.h"
@@ -96,7 +97,8 @@ void builtin_rhs_table(RhsTable &t)
 void builtin_hvp_table(HvpTable &t)
 {
     t = HvpTable{(int)sizeof(HvpTable), (int)sizeof(HvpArgs), (int)sizeof(PredictTlmArgs), (int)sizeof(LyapArgs),
-                 launch_hvp<RhsL96>, launch_predict_tlm<RhsL96, 0>, launch_lyap<RhsL96, 0>};
+                 (int)sizeof(PredictAdjArgs), launch_hvp<RhsL96>, launch_predict_tlm<RhsL96, 0>, launch_lyap<RhsL96, 0>,
+                 launch_predict_adj<RhsL96, 0>};
 }
 
 // ------------------------------------------------------------------ K2: tails as kernels of their own

@@ -18,6 +18,7 @@
 #include "va_persist.h"
 #include "va_predict.h"
 #include "va_predict_tlm.h"
+#include "va_predict_adj.h"
 #include "va_lyap.h"
 #include "va_hvp.h"
 
@@ -69,14 +70,15 @@ template <class R> void fill_table(va::RhsTable &t)
     if constexpr (va::rhs_flat<R>::value) { t.eval = va::eval_flat_op<R>; t.predict = va::launch_predict<R, R::D>; }
     if constexpr (va::seed_kernel_exists<R>()) t.seed = va::seed_op<R>;
 }
-// the Hessian-vector kernel, the tangent-linear predictor and the Lyapunov-spectrum kernel: derivatives of the element-wise
+// the Hessian-vector kernel, the tangent-linear predictor, its adjoint and the Lyapunov-spectrum kernel: derivatives of the element-wise
 // part only (a split-off linear part would need products of its own), and only where a flat struct exists
 template <class R> void fill_hvp_table(va::HvpTable &t)
 {
     t = va::HvpTable{(int)sizeof(va::HvpTable), (int)sizeof(va::HvpArgs), (int)sizeof(va::PredictTlmArgs), (int)sizeof(va::LyapArgs),
-                     nullptr, nullptr, nullptr};
+                     (int)sizeof(va::PredictAdjArgs), nullptr, nullptr, nullptr, nullptr};
     if constexpr (va::rhs_flat<R>::value && !va::rhs_linear<R>::value) {
         t.hvp = va::launch_hvp<R>; t.predict_tlm = va::launch_predict_tlm<R, R::D>;
+        t.predict_adj = va::launch_predict_adj<R, R::D>;
         if constexpr (R::D <= va::LYAP_MAX_D) t.lyap = va::launch_lyap<R, R::D>;
     }
 }

@@ -428,6 +428,97 @@ class Annealer(LadderAnnealer):
         out = out.reshape(len(sb), len(kb), out.shape[1], D)
         return out if self._batched else out[0]
 
+    def predict_vjp(self, G, n_steps, beta=None, seeds=None, substeps=1, every=1, stim=None):
+        """Sensitivity of a forecast functional to the estimate: one backward sweep through predict()'s RK4 steps per
+        cotangent set (csrc/va_predict_adj.h: the transpose of the derivative of the DISCRETE RK4 map).  G holds dJ / d(forecast
+        row): (ncot, n_out, D) for every selected point alike, or with predict()'s leading axes in front.  Selection and the
+        other arguments as predict().  Returns a dict: out, predict()'s forecast; gx0 (..., ncot, D) = dJ / d(last fitted
+        state); gp (..., ncot, NPest) = dJ / d(estimated parameters).  Time-dependent parameters: NotImplementedError."""
+        if self._pb is None or not getattr(self, "initalized", False):
+            raise ValueError("predict_vjp() works after anneal() / anneal_init()")
+        if self._tdp:
+            raise NotImplementedError("predict_vjp: time-dependent parameters are not carried")
+        sb, kb = self._select(beta, seeds)
+        N, D, NP, NX = self.N_model, self.D, self.NP, self._NX
+        npts = len(sb) * len(kb)
+        rows = self._mp[sb][:, kb].reshape(npts, -1)
+        G = np.asarray(G, dtype=np.float64)
+        if G.ndim == 3:
+            G = np.broadcast_to(G, (npts,) + G.shape)
+        G = np.ascontiguousarray(G.reshape((npts, -1) + G.shape[-2:]))
+        r = self._pb.predict_adjoint(rows[:, (N - 1) * D:N * D], rows[:, NX:], n_steps, G=G, t0=float(self.t_model[-1]),
+                                     substeps=substeps, every=every, stim=stim)
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        return {k: v.reshape(lead + v.shape[1:]) for k, v in r.items()}
+
+    SHOOT_OPT_ARGS = dict(ftol=1e-15, gtol=1e-9)
+
+    def _shoot_weights(self):
+        """weights (L,) with which va_predict_adjoint's cost is the action's measurement term as the package normalises it"""
+        if np.ndim(self.RM) == 3:
+            raise NotImplementedError("shoot: full RM matrices are not carried (the adjoint kernel's misfit takes one weight "
+                                      "per observed column)")
+        if isinstance(self.RM, np.ndarray):
+            if np.any(self.RM != self.RM[:1]):
+                raise NotImplementedError("shoot: RM changes along the data window; the adjoint kernel's misfit takes one "
+                                          "weight per observed column")
+            w = np.array(self.RM[0], dtype=np.float64)
+        else:
+            w = np.full(self.L, float(self.RM))
+        return w / (self.L * self.N_data)
+
+    def shoot(self, beta=-1, seeds=None, substeps=1, opt_args=None):
+        """The RF -> infinity limit, done exactly: strong-constraint 4D-Var refinement of the selected (seed, rung)s.  A
+        stored minimiser is a path, not a model orbit; this fits an actual model trajectory x(t; x(t_0), p) to the data
+        window.  From the first row of the stored minimiser and that rung's parameters, SciPy's L-BFGS-B (host, one point at a
+        time, the annealer's state and parameter bounds passed on) minimises over x(t_0) and the estimated parameters the
+        measurement term of the model trajectory -- the action's, as the package normalises it -- whose value and gradient
+        come from ONE device call per evaluation: the adjoint of the RK4 predictor in misfit mode (csrc/va_predict_adj.h).
+        Returns a dict with predict()'s leading axes: x0 (..., D), params (..., NP) the full vectors, path (..., N, D) the
+        model trajectory (predict()'s bits), cost, cost_start, grad_norm (largest gradient entry at the end), nfev, status
+        (SciPy's: 0 converged), path_distance: the RMS distance between the annealed path and the trajectory -- how far
+        from a model orbit that rung still is.  opt_args are SciPy's options on top of SHOOT_OPT_ARGS (the cost carries the
+        action's 1 / (L N_data), and SciPy's default ftol, relative to max(|f|, 1), would stop a well-fitted trajectory at
+        decreases of 2e-9).  Time-dependent parameters and full RM matrices: NotImplementedError."""
+        from scipy.optimize import minimize
+        if self._pb is None or not getattr(self, "initalized", False):
+            raise ValueError("shoot() works after anneal() / anneal_init()")
+        if self._tdp:
+            raise NotImplementedError("shoot: time-dependent parameters have no single model trajectory to fit")
+        w = self._shoot_weights()
+        sb, kb = self._select(beta, seeds)
+        N, D, NP, NPe, NX = self.N_model, self.D, self.NP, self.NPest, self._NX
+        Y = np.ascontiguousarray(self.Y, dtype=np.float64)
+        stim = None if self.stim is None else np.asarray(self.stim, dtype=np.float64)
+        t0, every, Pidx = float(self.t_model[0]), self.merr_nskip, list(self.Pidx)
+        bounds = None
+        if self.bounds is not None:
+            bounds = list(self.bounds[:D]) + list(self.bounds[NX:NX + NPe])
+        rows = self._mp[sb][:, kb].reshape(len(sb) * len(kb), -1)
+        res = dict(x0=[], params=[], path=[], cost=[], cost_start=[], grad_norm=[], nfev=[], status=[], path_distance=[])
+        for row in rows:
+            P = np.array(row[NX:NX + NP])
+
+            def fun(z):
+                P[Pidx] = z[D:]
+                r = self._pb.predict_adjoint(z[:D], P, N - 1, Y=Y, weights=w, t0=t0, substeps=substeps, every=every, stim=stim)
+                return float(r["cost"][0]), np.append(r["gx0"][0, 0], r["gp"][0, 0])
+            z0 = np.append(row[:D], P[Pidx])
+            c0 = fun(z0)[0]
+            opt = minimize(fun, z0, method="L-BFGS-B", jac=True, bounds=bounds, options=dict(self.SHOOT_OPT_ARGS, **(opt_args or {})))
+            c1, g1 = fun(opt.x)
+            path = self._pb.predict(opt.x[:D], P, N - 1, t0=t0, substeps=substeps, stim=stim)[0]
+            res["x0"].append(opt.x[:D]); res["params"].append(P.copy()); res["path"].append(path)
+            res["cost"].append(c1); res["cost_start"].append(c0); res["grad_norm"].append(np.abs(g1).max())
+            res["nfev"].append(opt.nfev + 2); res["status"].append(opt.status)
+            res["path_distance"].append(np.sqrt(np.mean((row[:NX].reshape(N, D) - path) ** 2)))
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        out = {}
+        for k, v in res.items():
+            v = np.array(v, dtype=np.int64 if k in ("nfev", "status") else np.float64)
+            out[k] = v.reshape(lead + v.shape[1:])
+        return out
+
     def prediction_error(self, Y_future, **predict_kwargs):
         """RMS error of the forecast against held-back observations: Y_future (n_out, L), the Lidx columns at the output
         times of predict(n_steps = (n_out - 1) * every, ...), row 0 being the last fitted time (not counted).  Per
