@@ -12,7 +12,7 @@ from every rung's estimate (Annealer.predict) and prints the forecast's RMS erro
 estimate, the forecast horizon 1 / lambda_1 in units of dt_model, the Kaplan-Yorke dimension (Annealer.lyapunov) and the
 largest conditional exponent with a gain on the measured columns (Annealer.sync_exponents).
 
-    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40] [--spread 40] [--lyapunov 4000] [--shoot]
+    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40] [--spread 40] [--lyapunov 4000] [--shoot [--shoot-device]]
 """
 import argparse
 import os
@@ -46,6 +46,8 @@ def main():
                     help="print lambda_1, the horizon 1 / lambda_1 in steps of dt_model, the Kaplan-Yorke dimension and the largest "
                          "conditional exponent at a few gains on the measured columns, over N model steps (a multiple of 4) from the "
                          "last rung's estimate (Annealer.lyapunov, Annealer.sync_exponents)")
+    ap.add_argument("--shoot-device", action="store_true",
+                    help="with --shoot: run the minimiser on the device too, all seeds in one launch (Annealer.shoot(device=True))")
     ap.add_argument("--shoot", action="store_true",
                     help="refine the last rung to a model trajectory (strong-constraint fit of x(t_0) and k: Annealer.shoot) and "
                          "print k, cost, path_distance and, with --predict N, the forecast error from its end beside the one "
@@ -158,10 +160,10 @@ def main():
     if args.shoot:
         # the RF -> infinity limit done exactly: a model trajectory fitted to the data window from the last rung's first
         # row and parameters; its end is on a model orbit, the annealed path's last row carries that rung's model error
-        sh = anneal1.shoot(beta=-1)
+        sh = anneal1.shoot(beta=-1, device=args.shoot_device)
         ks, cost, dist = np.ravel(sh["params"][..., 0]), np.ravel(sh["cost"]), np.ravel(sh["path_distance"])
         ends, pars = sh["path"].reshape(-1, N_model, D)[:, -1], sh["params"].reshape(-1, 1)
-        print("\nmodel trajectory fitted to the data window from the last rung (Annealer.shoot)")
+        print("\nmodel trajectory fitted to the data window from the last rung (Annealer.shoot%s)" % (", minimiser on the device" if args.shoot_device else ""))
         for b in range(ks.size):
             line = "seed %d   k = %.5f   cost = %.6g   path_distance = %.4g" % (b, ks[b], cost[b], dist[b])
             if held_back is not None:

@@ -307,6 +307,29 @@ int va_predict_adjoint(va_handle h, const double *x0, const double *p, const dou
                        int32_t y_shared, int32_t T, int32_t ncot, double t0, int32_t n_steps, int32_t substeps, int32_t every,
                        const double *stim, double *out, double *gx0, double *gp, double *cost);
 
+/* Strong-constraint shooting on the device (csrc/va_shoot.h): for each of T points, minimise va_predict_adjoint's misfit
+ *     cost(x0, p_est) = sum over rows and columns of w_l (x_l(t; x0, p) - y_l)^2
+ * over x0 and the handle's estimated parameters by L-BFGS (what SciPy's L-BFGS-B does without bounds: dcsrch line search, m
+ * history pairs), all points in ONE launch per chunk of points: a point's workgroup evaluates cost and gradient with the
+ * adjoint predictor's phases and steps the point's minimiser, evaluation after evaluation, without returning to the host.
+ *   x0 [T*D], p [T*NP] the starts (full parameter vectors); Y, weights, y_shared, t0, n_steps, substeps, every, stim as in
+ *        va_predict_adjoint's misfit mode
+ *   m history pairs (1 .. 32); maxiter >= 1; 1 <= maxfun <= 100000; maxls >= 1 trials per line search; ftol, gtol: stop when
+ *        f_old - f <= ftol max(|f_old|, |f|, 1), or when the largest gradient entry <= gtol
+ *   x0_out [T*D], p_out [T*NP] the returned points (full vectors; entries that are not estimated are the caller's);
+ *   cost [T], cost_start [T]; grad_max [T] the largest gradient entry at the returned point; nit [T]; nfev [T] (<= maxfun + 1);
+ *   status [T]: 0 converged, 1 maxiter or maxfun reached, 2 abnormal line search, 3 the cost at the start was not finite
+ *        (that point comes back unchanged; nothing raises).  A finite iterate is what comes back in every case.
+ * All arrays HOST.  No atomics, every sum in index order: the same bits on every call, and whichever points share a launch.
+ * The handle's resident paths, seed states and captured graphs are left alone.
+ * VA_EINVAL: what va_predict_adjoint rejects in misfit mode; m, maxiter, maxfun or maxls out of range.
+ * VA_EUNSUPPORTED (reason in va_last_error): what va_predict_adjoint refuses; D > 512; a handle with box bounds (no projected
+ * step yet). */
+int va_shoot(va_handle h, const double *x0, const double *p, const double *Y, const double *weights, int32_t y_shared, int32_t T,
+             double t0, int32_t n_steps, int32_t substeps, int32_t every, const double *stim, int32_t m, int64_t maxiter,
+             int64_t maxfun, int32_t maxls, double ftol, double gtol, double *x0_out, double *p_out, double *cost,
+             double *cost_start, double *grad_max, int32_t *nit, int32_t *nfev, int32_t *status);
+
 /* Lyapunov spectra of the handle's model (csrc/va_lyap.h): T trajectories from x0 with the parameters p, each with K <= D
  * tangents carried by the tangent-linear model of the RK4 integrator (va_predict's steps, stage times and stimulus; the
  * parameter tangent is zero) and re-orthonormalised together by a thin QR with positive diagonal after every qr_every model

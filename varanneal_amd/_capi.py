@@ -210,6 +210,9 @@ def lib():
     L.va_predict_adjoint.argtypes = [h, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                      C.c_int32] + [c_dp] * 5
     L.va_predict_adjoint.restype = C.c_int
+    L.va_shoot.argtypes = [h, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_dp, C.c_int32,
+                           C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double] + [c_dp] * 5 + [c_ip] * 3
+    L.va_shoot.restype = C.c_int
     L.va_lyapunov.argtypes = [h, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double] + [C.c_int32] * 4 + [c_dp] * 5 + [c_ip]
     L.va_lyapunov.restype = C.c_int
     L.va_hess_vec.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, c_dp]
@@ -255,7 +258,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_eval_grid", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_predict_adjoint", "va_lyapunov", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_predict_adjoint", "va_shoot", "va_lyapunov", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -598,6 +601,47 @@ class Problem(object):
         ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
         check(self._L.va_predict_adjoint(self._h, ptr(x0), ptr(p), ptr(G), ptr(Y), ptr(w), shared, T, ncot, float(t0), n_steps, substeps,
                                          every, ptr(st), ptr(r["out"]), ptr(r["gx0"]), ptr(r["gp"]), ptr(r.get("cost"))))
+        return r
+
+    def shoot(self, x0, p, n_steps, Y, weights, t0=0.0, substeps=1, every=1, stim=None, m=10, maxiter=15000, maxfun=15000, maxls=20,
+              ftol=1e-15, gtol=1e-9):
+        """Strong-constraint shooting on the device (va_shoot; csrc/va_shoot.h): from each of the T starts x0 (T, D) with the
+        full parameter vectors p (T, NP), minimise predict_adjoint's misfit cost = sum w (x - y)^2 over x0 and the estimated
+        parameters by L-BFGS -- SciPy's L-BFGS-B without bounds: m pairs, ftol, gtol, maxiter, maxfun, maxls -- every point's
+        whole minimisation in one launch.  Y (T, n_out, L) or (n_out, L), weights (L,), t0, substeps, every, stim as in
+        predict_adjoint.  Returns a dict: x0 (T, D), p (T, NP) the returned points (full vectors), cost, cost_start, grad_max
+        (largest gradient entry at the returned point), nit, nfev, status (T,): 0 converged, 1 maxiter / maxfun, 2 abnormal
+        line search, 3 non-finite cost at the start (the point comes back unchanged).  D <= 512; a handle with bounds is refused."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("shoot: a network handle has no differential equation to integrate")
+        D, NP, Ld = self.desc.D, self.desc.NP, self.desc.L
+        x0 = _f64(x0).reshape(-1, D)
+        T = x0.shape[0]
+        p = _f64(p).reshape(-1, NP) if NP else np.zeros((T, 0))
+        if p.shape[0] == 1 and T > 1:
+            p = np.ascontiguousarray(np.broadcast_to(p, (T, NP)))
+        if p.shape[0] != T:
+            raise ValueError("shoot: %d states but %d parameter vectors" % (T, p.shape[0]))
+        n_steps, substeps, every = int(n_steps), int(substeps), int(every)
+        n_out = n_steps // every + 1 if every >= 1 and n_steps >= 1 else 1
+        st = None
+        if stim is not None:
+            st = _f64(stim).reshape(max(n_steps, 0) + 1, -1)
+            if st.shape[1] != self.desc.n_stim and self.desc.n_stim:
+                raise ValueError("shoot: the stimulus must have %d rows of %d column(s)" % (n_steps + 1, self.desc.n_stim))
+        Y = _f64(Y)
+        if Y.shape not in ((n_out, Ld), (T, n_out, Ld)):
+            raise ValueError("shoot: Y must have shape (n_out = %d, L = %d) or (%d, %d, %d), got %s" % (n_out, Ld, T, n_out, Ld, Y.shape))
+        w = _f64(weights)
+        if w.shape != (Ld,):
+            raise ValueError("shoot: weights must have shape (L = %d,), got %s" % (Ld, w.shape))
+        r = dict(x0=np.empty((T, D)), p=np.empty((T, NP)), cost=np.empty(T), cost_start=np.empty(T), grad_max=np.empty(T),
+                 nit=np.empty(T, dtype=np.int32), nfev=np.empty(T, dtype=np.int32), status=np.empty(T, dtype=np.int32))
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
+        iptr = lambda a: a.ctypes.data_as(c_ip)
+        check(self._L.va_shoot(self._h, ptr(x0), ptr(p), ptr(Y), ptr(w), 1 if Y.ndim == 2 else 0, T, float(t0), n_steps, substeps, every,
+                               ptr(st), int(m), int(maxiter), int(maxfun), int(maxls), float(ftol), float(gtol), ptr(r["x0"]), ptr(r["p"]),
+                               ptr(r["cost"]), ptr(r["cost_start"]), ptr(r["grad_max"]), iptr(r["nit"]), iptr(r["nfev"]), iptr(r["status"])))
         return r
 
     def lyapunov(self, x0, p, K, n_steps, t0=0.0, substeps=1, qr_every=1, n_skip=0, Q0=None, coupling=None, stim=None, trace=False):

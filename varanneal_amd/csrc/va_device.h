@@ -153,13 +153,16 @@ void builtin_rhs_table(RhsTable &t);
 struct PredictTlmArgs;
 struct LyapArgs;
 struct PredictAdjArgs;
+struct ShootArgs;
 struct HvpTable {
     int bytes, hvp_bytes, tlm_bytes, lyap_bytes;      // sizeof(HvpTable), sizeof(HvpArgs), sizeof(PredictTlmArgs), sizeof(LyapArgs)
     int adj_bytes;                                    // sizeof(PredictAdjArgs)
+    int shoot_bytes;                                  // sizeof(ShootArgs)
     hipError_t (*hvp)(const HvpArgs &, size_t lds_bytes, hipStream_t);      // or NULL
     hipError_t (*predict_tlm)(const PredictTlmArgs &, hipStream_t);         // or NULL
     hipError_t (*lyap)(const LyapArgs &, hipStream_t);                      // or NULL
     hipError_t (*predict_adj)(const PredictAdjArgs &, hipStream_t);         // the adjoint predictor (va_predict_adj.h), or NULL
+    hipError_t (*shoot)(const ShootArgs &, hipStream_t);                    // the shooting kernel (va_shoot.h), or NULL
 };
 void builtin_hvp_table(HvpTable &t);
 

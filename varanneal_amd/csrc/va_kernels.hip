@@ -28,6 +28,7 @@
 #include "va_predict.h"
 #include "va_predict_tlm.h"
 #include "va_predict_adj.h"
+#include "va_shoot.h"
 #include "va_lyap.h"
 #include "va_hvp.h"
 #include "va_eval4_builtin.h"
@@ -93,12 +94,13 @@ void builtin_rhs_table(RhsTable &t)
     t = RhsTable{(int)sizeof(RhsTable), (int)sizeof(Dev), (int)sizeof(SeedState), (int)sizeof(PredictArgs), RhsL96::NP, 0, 0,
                  eval_builtin, nullptr, seed_op<RhsL96>, launch_predict<RhsL96, 0>};
 }
-// Hessian-vector products (va_hvp.h), the tangent-linear predictor (va_predict_tlm.h) and Lyapunov spectra (va_lyap.h)
+// Hessian-vector products (va_hvp.h), the tangent-linear predictor (va_predict_tlm.h), Lyapunov spectra (va_lyap.h), the
+// adjoint predictor (va_predict_adj.h) and the shooting kernel (va_shoot.h)
 void builtin_hvp_table(HvpTable &t)
 {
     t = HvpTable{(int)sizeof(HvpTable), (int)sizeof(HvpArgs), (int)sizeof(PredictTlmArgs), (int)sizeof(LyapArgs),
-                 (int)sizeof(PredictAdjArgs), launch_hvp<RhsL96>, launch_predict_tlm<RhsL96, 0>, launch_lyap<RhsL96, 0>,
-                 launch_predict_adj<RhsL96, 0>};
+                 (int)sizeof(PredictAdjArgs), (int)sizeof(ShootArgs), launch_hvp<RhsL96>, launch_predict_tlm<RhsL96, 0>,
+                 launch_lyap<RhsL96, 0>, launch_predict_adj<RhsL96, 0>, launch_shoot<RhsL96, 0>};
 }
 
 // ------------------------------------------------------------------ K2: tails as kernels of their own

@@ -467,7 +467,9 @@ class Annealer(LadderAnnealer):
             w = np.full(self.L, float(self.RM))
         return w / (self.L * self.N_data)
 
-    def shoot(self, beta=-1, seeds=None, substeps=1, opt_args=None):
+    _SHOOT_DEVICE_OPTS = dict(ftol="ftol", gtol="gtol", maxiter="maxiter", maxfun="maxfun", maxcor="m", maxls="maxls")
+
+    def shoot(self, beta=-1, seeds=None, substeps=1, opt_args=None, device=False):
         """The RF -> infinity limit, done exactly: strong-constraint 4D-Var refinement of the selected (seed, rung)s.  A
         stored minimiser is a path, not a model orbit; this fits an actual model trajectory x(t; x(t_0), p) to the data
         window.  From the first row of the stored minimiser and that rung's parameters, SciPy's L-BFGS-B (host, one point at a
@@ -479,7 +481,15 @@ class Annealer(LadderAnnealer):
         (SciPy's: 0 converged), path_distance: the RMS distance between the annealed path and the trajectory -- how far
         from a model orbit that rung still is.  opt_args are SciPy's options on top of SHOOT_OPT_ARGS (the cost carries the
         action's 1 / (L N_data), and SciPy's default ftol, relative to max(|f|, 1), would stop a well-fitted trajectory at
-        decreases of 2e-9).  Time-dependent parameters and full RM matrices: NotImplementedError."""
+        decreases of 2e-9).  Time-dependent parameters and full RM matrices: NotImplementedError.
+        device=True: the minimiser runs on the device too -- all selected (seed, rung)s go through ONE Problem.shoot call
+        (csrc/va_shoot.h: every point's L-BFGS from the first evaluation to the last inside one launch), then one predict()
+        call for path.  The same keys, shapes and meanings, plus nit (iterations); nfev counts the kernel's evaluations;
+        status 1 budget, 2 abnormal line search, 3 non-finite cost at the start.  opt_args: ftol, gtol, maxiter, maxfun,
+        maxcor, maxls (any other key: ValueError).  Annealer bounds: NotImplementedError (no projected step on the device);
+        D <= 512."""
+        if device:
+            return self._shoot_device(beta, seeds, substeps, opt_args)
         from scipy.optimize import minimize
         if self._pb is None or not getattr(self, "initalized", False):
             raise ValueError("shoot() works after anneal() / anneal_init()")
@@ -516,6 +526,38 @@ class Annealer(LadderAnnealer):
         out = {}
         for k, v in res.items():
             v = np.array(v, dtype=np.int64 if k in ("nfev", "status") else np.float64)
+            out[k] = v.reshape(lead + v.shape[1:])
+        return out
+
+    def _shoot_device(self, beta, seeds, substeps, opt_args):
+        if self._pb is None or not getattr(self, "initalized", False):
+            raise ValueError("shoot() works after anneal() / anneal_init()")
+        if self._tdp:
+            raise NotImplementedError("shoot: time-dependent parameters have no single model trajectory to fit")
+        if self.bounds is not None:
+            raise NotImplementedError("shoot(device=True): bounds are not carried (the device minimiser takes no projected step); "
+                                      "use device=False")
+        kw = {}
+        for k, v in dict(self.SHOOT_OPT_ARGS, **(opt_args or {})).items():
+            if k not in self._SHOOT_DEVICE_OPTS:
+                raise ValueError("shoot(device=True): option %r is not carried (known: %s)" % (k, ", ".join(sorted(self._SHOOT_DEVICE_OPTS))))
+            kw[self._SHOOT_DEVICE_OPTS[k]] = v
+        w = self._shoot_weights()
+        sb, kb = self._select(beta, seeds)
+        N, D, NP, NX = self.N_model, self.D, self.NP, self._NX
+        stim = None if self.stim is None else np.asarray(self.stim, dtype=np.float64)
+        t0 = float(self.t_model[0])
+        rows = self._mp[sb][:, kb].reshape(len(sb) * len(kb), -1)
+        r = self._pb.shoot(rows[:, :D], rows[:, NX:NX + NP], N - 1, np.ascontiguousarray(self.Y, dtype=np.float64), w, t0=t0,
+                           substeps=substeps, every=self.merr_nskip, stim=stim, **kw)
+        path = self._pb.predict(r["x0"], r["p"], N - 1, t0=t0, substeps=substeps, stim=stim)
+        res = dict(x0=r["x0"], params=r["p"], path=path, cost=r["cost"], cost_start=r["cost_start"], grad_norm=r["grad_max"],
+                   nfev=r["nfev"], nit=r["nit"], status=r["status"],
+                   path_distance=np.sqrt(np.mean((rows[:, :NX].reshape(-1, N, D) - path) ** 2, axis=(1, 2))))
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        out = {}
+        for k, v in res.items():
+            v = np.array(v, dtype=np.int64 if k in ("nfev", "nit", "status") else np.float64)
             out[k] = v.reshape(lead + v.shape[1:])
         return out
 
