@@ -25,13 +25,29 @@ steps and columns that may cancel, so its relative error is the larger one).  Th
 contraction and summation order gives 5.1e-11.  The gradients grow backward along the horizon as the tangents grow forward
 (entries of 10 to 60 from unit cotangents), hence relative per row.  A wrong coefficient, a stage cotangent applied at
 another stage's linearisation point, or a row's cotangent taken a step late shows at 1e-4 or worse.  Do not lengthen the
-horizon without deriving this again."""
+horizon without deriving this again.
+
+The wide shapes of _forecast_shapes.SLOTS_WIDE ((D, ncot) = (33, 2) ... (1024, 1), 3 attractor states, cotangent mode) keep
+TOL_ADJ: derive_wide() measures between 4.5e-15 and 1.49e-13 (D = 200, substeps = 1; 7.7e-14 at D = 100, 1.8e-14 at D = 1024;
+gx0 entries up to 615), and 250 x 1.49e-13 = 3.7e-11 stays under 5.1e-11.
+
+TOL_ADJ_MISFIT_WIDE: misfit mode at D = 300 and 1024 (misfit_inputs(): every third column observed, (substeps, every) =
+(2, 3)), used by the tests of those two shapes only.  There the cotangents 2 w (x - y) are the observation noise, and the
+one-entry gp row sums them over all steps and columns with more cancellation than standard normal cotangents leave:
+derive_wide() measures, over cost, gx0 rows and gp rows, 1.32e-12 at D = 300 and 3.3e-13 at D = 1024.  250 x 1.32e-12 =
+3.3e-10 is past TOL_ADJ, so these two calls take 3.3e-10 with the same 250-fold margin.
+
+The transpose identity <G, dX_c> = <gx0, v_x> + gp v_p, relative to |G| |dX_c| as test_transpose_of_the_tangent_kernel forms
+it, keeps that test's TOL + TOL_ADJ = 5.9e-11 at the wide shapes: derive_transpose() finds the float64 reference pair off by
+4.5e-18 (D = 1024) to 6.9e-17 (D = 33) with the sums in float64, the longdouble pair by 4e-21 to 4e-20 (the references are
+transposes of each other; what the float64 pair leaves is rounding), and 250 x 6.9e-17 = 1.7e-14 is far under 5.9e-11."""
 import numpy as np
 
 import _tlm_ref
 from _predict_ref import DT, K_TRUE, STEPS, attractor_starts, l96
 
 TOL_ADJ = 5.1e-11
+TOL_ADJ_MISFIT_WIDE = 3.3e-10
 
 
 def l96_vjp(t, x, p, st, s):
@@ -200,7 +216,91 @@ def derive(widths=(5, 20, 64, 67), T=7, ncot=3):
     return worst
 
 
+def misfit_inputs(D, T, substeps=2, every=3):
+    """misfit mode at a wide shape: (x0 (T, D), Lidx: every third column, w (L,), Y (T, n_out, L): the NumPy trajectory's
+    observed columns + 0.3 randn)"""
+    from _predict_ref import l96_reference
+    x0, ref_x = l96_reference(D, T, substeps, every)
+    Lidx = list(range(0, D, 3))
+    rng = np.random.RandomState(40 + D)
+    w = (0.5 + rng.rand(len(Lidx))) / len(Lidx)
+    return x0, Lidx, w, ref_x[:, :, Lidx] + 0.3 * rng.randn(T, ref_x.shape[1], len(Lidx))
+
+
+def derive_wide(misfit_widths=(300, 1024)):
+    """the same figure at the wide shapes of _forecast_shapes.SLOTS_WIDE with their T = 3, and in misfit mode (cost,
+    gx0, gp relative) at misfit_widths"""
+    import _forecast_shapes as fs
+    ld = np.longdouble
+    worst = {}
+    for (D, ncot), _, _ in fs.SLOTS_WIDE:
+        x0 = attractor_starts(D, fs.T)
+        for substeps, every in ((1, 1), (2, 3)):
+            G = cotangents(D, fs.T, ncot, STEPS // every + 1)
+            e, big = 0.0, 0.0
+            for i in range(fs.T):
+                a = adj_rk4(l96, l96_vjp, l96_pgrad, x0[i], K_TRUE, G[i], STEPS, DT, substeps=substeps, every=every)
+                b = adj_rk4(l96, l96_vjp, l96_pgrad, x0[i], K_TRUE, G[i], STEPS, DT, substeps=substeps, every=every, dtype=ld)
+                for k in (1, 2):
+                    e = max(e, row_error(np.asarray(a[k], dtype=ld), b[k]))
+                big = max(big, float(np.abs(b[1]).max()))
+            worst[(D, ncot, substeps, every)] = e
+            print("D=%d ncot=%d substeps=%d every=%d  float64 vs longdouble, relative per row: %.2e  largest gx0 entry %.3g"
+                  % (D, ncot, substeps, every, e, big))
+    for D in misfit_widths:
+        x0, Lidx, w, Y = misfit_inputs(D, fs.T)
+        e = 0.0
+        for i in range(fs.T):
+            out = rk4_ld(x0[i], 2, 3)
+            Gl, cl = misfit_cotangent(out, np.asarray(Y[i], dtype=ld), Lidx, np.asarray(w, dtype=ld))
+            _, gl, ql = adj_rk4(l96, l96_vjp, l96_pgrad, x0[i], K_TRUE, Gl, STEPS, DT, substeps=2, every=3, dtype=ld)
+            c, g, q, _ = misfit_rk4(l96, l96_vjp, l96_pgrad, x0[i], K_TRUE, Y[i], Lidx, w, STEPS, DT, substeps=2, every=3)
+            e = max(e, abs(c - cl) / cl, row_error(np.asarray(g, dtype=ld), gl[0]), row_error(np.asarray(q, dtype=ld), ql[0]))
+        worst[(D, "misfit")] = float(e)
+        print("D=%d misfit mode (2, 3)  float64 vs longdouble, cost and gradient rows relative: %.2e" % (D, e))
+    return worst
+
+
+def rk4_ld(x0, substeps, every):
+    from _predict_ref import rk4
+    return rk4(l96, x0, K_TRUE, STEPS, DT, substeps=substeps, every=every, dtype=np.longdouble)
+
+
+def derive_transpose():
+    """the transpose identity at the wide shapes, as the tests form it: <G, dX_c> - (<gx0, v_x> + gp v_p) relative to
+    |G| |dX_c| with the float64 reference pair (sums in float64), beside the same defect of the pair in longdouble (which
+    shows that what the float64 pair leaves is rounding, not a property of the references)"""
+    import _forecast_shapes as fs
+    ld = np.longdouble
+    worst = {}
+    for (D, n), _, _ in fs.SLOTS_WIDE:
+        x0, V = attractor_starts(D, fs.T), fs.directions(D, n)
+        substeps, every = 2, 3
+        G = cotangents(D, fs.T, n, STEPS // every + 1)
+        e, el = 0.0, 0.0
+        for i in range(fs.T):
+            for dt_, which in ((np.float64, 0), (ld, 1)):
+                _, dX = _tlm_ref.tlm_rk4(l96, _tlm_ref.l96_jvp, x0[i], K_TRUE, V, STEPS, DT, substeps=substeps, every=every, dtype=dt_)
+                _, gx0, gp = adj_rk4(l96, l96_vjp, l96_pgrad, x0[i], K_TRUE, G[i], STEPS, DT, substeps=substeps, every=every, dtype=dt_)
+                Gi, Vi = np.asarray(G[i], dtype=dt_), np.asarray(V, dtype=dt_)
+                for g in range(n):
+                    for c in range(n):
+                        d = abs((Gi[g] * dX[c]).sum() - ((gx0[g] * Vi[c, :D]).sum() + gp[g, 0] * Vi[c, D]))
+                        d = float(d / (np.linalg.norm(G[i, g]) * np.linalg.norm(np.asarray(dX[c], dtype=np.float64))))
+                        if which:
+                            el = max(el, d)
+                        else:
+                            e = max(e, d)
+        worst[(D, n)] = e
+        print("D=%d n=%d (2, 3)  transpose defect relative to |G| |dX_c|: float64 pair %.2e, longdouble pair %.2e" % (D, n, e, el))
+    return worst
+
+
 if __name__ == "__main__":
     print("self check: %.2e" % self_check())
     w = derive()
     print("largest %.2e  x 250 = %.2e" % (max(w.values()), 250 * max(w.values())))
+    w = derive_wide()
+    print("wide shapes: largest %.2e  x 250 = %.2e  (TOL_ADJ %.1e)" % (max(w.values()), 250 * max(w.values()), TOL_ADJ))
+    w = derive_transpose()
+    print("transpose identity: largest %.2e  x 250 = %.2e  (TOL + TOL_ADJ %.1e)" % (max(w.values()), 250 * max(w.values()), _tlm_ref.TOL + TOL_ADJ))

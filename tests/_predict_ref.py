@@ -11,10 +11,17 @@ TOL: |device or host C++ - NumPy| <= 1e-11 absolute on states of size 10-15, for
 trajectories in float64 and in longdouble differ by at most 4e-14 after 40 steps at D = 5 ... 200 (3e-12 after 80 steps at
 D = 200), which leaves a 250-fold margin for FMA contraction and summation order; a wrong coefficient or stage time
 shows at 1e-4 or worse.  The system is chaotic (roundoff alone reaches 4e-9 at 200 steps): do not lengthen the horizon
-without deriving this again."""
+without deriving this again.
+
+TOL_WIDE: the same bound for the wide states of _forecast_shapes.py (D = 257, 513, 769, 1024), used by the tests of those
+shapes only.  derive() (python tests/_predict_ref.py: 7 attractor states per width, both (substeps, every) pairs the tests
+use) gives, float64 against longdouble after 40 steps: at most 7.0e-14 over D = 5 ... 200; 6.6e-14 at D = 257, 8.0e-14 at
+513, 1.52e-13 at 769 ((2, 3); 8.0e-14 at (1, 1)) and 9.2e-14 at 1024, on states up to 14.4.  250 x 1.52e-13 = 3.8e-11 is
+past TOL, so the wide shapes take TOL_WIDE = 3.8e-11 with the same 250-fold margin; the older tests keep TOL."""
 import numpy as np
 
 TOL = 1e-11
+TOL_WIDE = 3.8e-11
 K_TRUE, DT, STEPS = 8.17, 0.025, 40
 
 
@@ -22,10 +29,11 @@ def l96(t, x, p, st=None):
     return np.roll(x, 1) * (np.roll(x, -1) - np.roll(x, 2)) - x + p
 
 
-def rk4(f, x0, p, n_steps, dt, t0=0.0, substeps=1, every=1, stim=None):
-    """f(t, x (D,), p, stimulus row or None) -> (D,).  Returns (n_steps // every + 1, D): steps 0, every, ..."""
-    h = dt / substeps
-    x = np.array(x0, dtype=np.float64)
+def rk4(f, x0, p, n_steps, dt, t0=0.0, substeps=1, every=1, stim=None, dtype=np.float64):
+    """f(t, x (D,), p, stimulus row or None) -> (D,).  Returns (n_steps // every + 1, D): steps 0, every, ...
+    dtype=np.longdouble carries the integration in extended precision (derive(); no stimulus there)."""
+    h = dtype(dt) / dtype(substeps)
+    x = np.array(x0, dtype=dtype)
     out = [x.copy()]
 
     def st(n, s, c):
@@ -76,3 +84,25 @@ def l96_reference(D, T, substeps=1, every=1, ks=None):
         ref.setflags(write=False)
         _refs[key] = (x0, ref)
     return _refs[key]
+
+
+def derive(widths=(5, 20, 64, 67, 200, 257, 513, 769, 1024), T=7):
+    """the figures of the docstring: float64 against longdouble, absolute, per width and (substeps, every)"""
+    worst = {}
+    for D in widths:
+        x0 = attractor_starts(D, T)
+        for substeps, every in ((1, 1), (2, 3)):
+            e, big = 0.0, 0.0
+            for i in range(T):
+                a = rk4(l96, x0[i], K_TRUE, STEPS, DT, substeps=substeps, every=every)
+                b = rk4(l96, x0[i], K_TRUE, STEPS, DT, substeps=substeps, every=every, dtype=np.longdouble)
+                e = max(e, float(np.abs(np.asarray(a, dtype=np.longdouble) - b).max()))
+                big = max(big, float(np.abs(b).max()))
+            worst[(D, substeps, every)] = e
+            print("D=%d substeps=%d every=%d  float64 vs longdouble, absolute: %.2e  largest state %.3g" % (D, substeps, every, e, big))
+    return worst
+
+
+if __name__ == "__main__":
+    w = derive()
+    print("largest %.2e  x 250 = %.2e  (TOL %.1e)" % (max(w.values()), 250 * max(w.values()), TOL))

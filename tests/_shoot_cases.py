@@ -21,26 +21,41 @@ WIDTHS = {5: 7, 20: 7, 33: 7, 130: 2}             # D -> points
 _cases, _refs = {}, {}
 
 
+def _build(D, T):
+    truth = attractor_starts(D, T)
+    Y, x0 = np.empty((T, N_ROWS, D)), np.empty((T, D))
+    for j in range(T):
+        rng = np.random.RandomState(100 + j)
+        Y[j] = rk4(l96, truth[j], K_TRUE, N_ROWS - 1, DT) + NOISE * rng.randn(N_ROWS, D)
+        x0[j] = truth[j] + OFF * rng.randn(D)
+    c = dict(truth=np.array(truth), Y=Y, x0=x0, k=np.full(T, K_START), w=np.full(D, 1.0 / (D * N_ROWS)))
+    for v in c.values():
+        v.setflags(write=False)
+    return c
+
+
 def case(D):
     """dict: truth (T, D), Y (T, N, D), x0 (T, D) the starts, k (T,), w (D,)"""
     if D not in _cases:
-        T = WIDTHS[D]
-        truth = attractor_starts(D, T)
-        Y, x0 = np.empty((T, N_ROWS, D)), np.empty((T, D))
-        for j in range(T):
-            rng = np.random.RandomState(100 + j)
-            Y[j] = rk4(l96, truth[j], K_TRUE, N_ROWS - 1, DT) + NOISE * rng.randn(N_ROWS, D)
-            x0[j] = truth[j] + OFF * rng.randn(D)
-        c = dict(truth=np.array(truth), Y=Y, x0=x0, k=np.full(T, K_START), w=np.full(D, 1.0 / (D * N_ROWS)))
-        for v in c.values():
-            v.setflags(write=False)
-        _cases[D] = c
+        _cases[D] = _build(D, WIDTHS[D])
     return _cases[D]
+
+
+_wide = {}
+
+
+def wide_case(D, T=2):
+    """the same family at a width outside WIDTHS (the wide lane geometries of _forecast_shapes.SHOOT_WIDE), for runs that
+    stop at a budget: there is no convergence reference at these widths and reference() does not take them"""
+    if (D, T) not in _wide:
+        _wide[(D, T)] = _build(D, T)
+    return _wide[(D, T)]
 
 
 def misfit(D, z, Y):
     """(cost, gradient (D + 1,)) at z = [x0 | k] by the NumPy adjoint"""
-    c, gx, gp, _ = _adj_ref.misfit_rk4(l96, _adj_ref.l96_vjp, _adj_ref.l96_pgrad, z[:D], z[D], Y, range(D), case(D)["w"], N_ROWS - 1, DT)
+    w = np.full(D, 1.0 / (D * N_ROWS))                # (case(D)["w"], at any width)
+    c, gx, gp, _ = _adj_ref.misfit_rk4(l96, _adj_ref.l96_vjp, _adj_ref.l96_pgrad, z[:D], z[D], Y, range(D), w, N_ROWS - 1, DT)
     return c, np.append(gx, gp)
 
 

@@ -19,7 +19,12 @@ longdouble for 40 steps of dt = 0.025 from 7 attractor states with the D + 1 dir
 64, 67, 200 and both (substeps, every) pairs the tests use; the largest difference relative to the row's largest entry is
 3.12e-14 (D = 200, substeps = 1; between 4.1e-15 and 3.1e-14 over the cases).  The same 250-fold margin for FMA
 contraction and summation order gives 7.8e-12.  A wrong coefficient or stage time, or a tangent stage that reads the
-nominal input of another stage, shows at 1e-4 or worse.  Do not lengthen the horizon without deriving this again."""
+nominal input of another stage, shows at 1e-4 or worse.  Do not lengthen the horizon without deriving this again.
+
+The wide shapes of _forecast_shapes.SLOTS_WIDE ((D, nvec) = (33, 2) ... (1024, 1), 3 attractor states, the mixed random
+directions of _forecast_shapes.directions) keep TOL: derive_wide() measures between 3.8e-15 and 2.71e-14 (D = 700,
+substeps = 1; 2.5e-14 at D = 513, 2.0e-14 at D = 1024; tangent entries up to 175), and 250 x 2.71e-14 = 6.8e-12 stays
+under 7.8e-12."""
 import numpy as np
 
 from _predict_ref import DT, K_TRUE, STEPS, attractor_starts, l96, rk4
@@ -168,7 +173,27 @@ def derive(widths=(5, 20, 64, 67, 200), T=7):
     return worst
 
 
+def derive_wide():
+    """the same figure at the wide shapes of _forecast_shapes.SLOTS_WIDE with their mixed directions and their T = 3"""
+    import _forecast_shapes as fs
+    worst = {}
+    for (D, nvec), _, _ in fs.SLOTS_WIDE:
+        x0, V = attractor_starts(D, fs.T), fs.directions(D, nvec)
+        for substeps, every in ((1, 1), (2, 3)):
+            e = 0.0
+            for i in range(fs.T):
+                a = tlm_rk4(l96, l96_jvp, x0[i], K_TRUE, V, STEPS, DT, substeps=substeps, every=every)[1]
+                b = tlm_rk4(l96, l96_jvp, x0[i], K_TRUE, V, STEPS, DT, substeps=substeps, every=every, dtype=np.longdouble)[1]
+                e = max(e, row_error(np.asarray(a, dtype=np.longdouble), b))
+            worst[(D, nvec, substeps, every)] = e
+            print("D=%d nvec=%d substeps=%d every=%d  float64 vs longdouble, relative per row: %.2e  largest tangent entry %.3g"
+                  % (D, nvec, substeps, every, e, float(np.abs(b).max())))
+    return worst
+
+
 if __name__ == "__main__":
     print("self check: %.2e" % self_check())
     w = derive()
     print("largest %.2e  x 250 = %.2e" % (max(w.values()), 250 * max(w.values())))
+    w = derive_wide()
+    print("wide shapes, mixed directions: largest %.2e  x 250 = %.2e  (TOL %.1e)" % (max(w.values()), 250 * max(w.values()), TOL))

@@ -6,7 +6,7 @@
 //        every workgroup carries the nominal columns of its live trajectories exactly once (nom = 1)
 //   predict_tlm_check traj D T nvec n_steps substeps every dt in out -> Lorenz-96 through predict_tlm_host and spread_host (the
 //        kernels' phases, lane by lane): `in` holds T*D start values, T forcings, T*nvec*(D+1) directions as text; `out`
-//        receives out, dX, var, cov as raw doubles
+//        receives out, dX, var, cov as raw doubles; a last argument "nocov" leaves cov out (wide states: T n_out D D doubles)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -75,7 +75,8 @@ int main(int argc, char **argv)
         }
         return 0;
     }
-    if (argc != 11 || strcmp(argv[1], "traj")) return 2;
+    const bool nocov = argc == 12 && !strcmp(argv[11], "nocov");
+    if ((argc != 11 && !nocov) || strcmp(argv[1], "traj")) return 2;
     va::PredictTlmArgs a;
     a.D = atoi(argv[2]); a.T = atoi(argv[3]); a.nvec = atoi(argv[4]); a.n_steps = atoi(argv[5]); a.substeps = atoi(argv[6]);
     a.every = atoi(argv[7]); a.dt = atof(argv[8]); a.t0 = 0.0; a.NP = va::RhsL96::NP; a.NPest = 1; a.nstim = 0; a.stim = nullptr;
@@ -83,7 +84,7 @@ int main(int argc, char **argv)
     if (!va::plan_predict_tlm(a.D, a.T, a.nvec, a.NP, a.nstim, a.geo)) { fprintf(stderr, "refused: %s\n", a.geo.why); return 3; }
     const size_t row = (size_t)a.n_out * a.D;
     std::vector<double> x0((size_t)a.T * a.D), p((size_t)a.T), V0((size_t)a.T * a.nvec * (a.D + 1)), out(a.T * row, -1.0),
-        dX(a.T * a.nvec * row, -1.0), var(a.T * row, -1.0), cov(a.T * row * a.D, -1.0);
+        dX(a.T * a.nvec * row, -1.0), var(a.T * row, -1.0), cov(nocov ? 0 : a.T * row * a.D, -1.0);
     FILE *fh = fopen(argv[9], "r");
     if (!fh) return 4;
     for (double &v : x0) if (fscanf(fh, "%lf", &v) != 1) return 5;
@@ -94,7 +95,7 @@ int main(int argc, char **argv)
     a.x0 = x0.data(); a.p = p.data(); a.V0 = V0.data(); a.Pidx = &pidx; a.out = out.data(); a.dX = dX.data();
     va::predict_tlm_host<va::RhsL96>(a);
     va::SpreadArgs sa;
-    sa.dX = dX.data(); sa.var = var.data(); sa.cov = cov.data(); sa.T = a.T; sa.nvec = a.nvec; sa.n_out = a.n_out; sa.D = a.D;
+    sa.dX = dX.data(); sa.var = var.data(); sa.cov = nocov ? nullptr : cov.data(); sa.T = a.T; sa.nvec = a.nvec; sa.n_out = a.n_out; sa.D = a.D;
     va::spread_host(sa);
     fh = fopen(argv[10], "wb");
     if (!fh) return 6;
