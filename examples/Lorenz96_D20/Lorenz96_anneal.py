@@ -8,11 +8,13 @@ the data file location.  Optional: --seeds B runs B random initial paths as one 
 from every rung's estimate (Annealer.predict) and prints the forecast's RMS error per rung;
 --spread N holds them back as well and prints the last rung's forecast with its +- 2 sigma band
 (Annealer.predict_spread) and the share of held-back observed values inside it at a few lead times;
+--track N holds them back too and carries the last rung's estimate through them with an ensemble Kalman filter on the device
+(Annealer.track), printing per seed the RMS error of the analysis mean on the observed and the unobserved columns beside predict()'s.
 --lyapunov N prints, per seed, the leading Lyapunov exponent of the estimated model over N steps from the last rung's
 estimate, the forecast horizon 1 / lambda_1 in units of dt_model, the Kaplan-Yorke dimension (Annealer.lyapunov) and the
 largest conditional exponent with a gain on the measured columns (Annealer.sync_exponents).
 
-    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40] [--spread 40] [--lyapunov 4000] [--shoot [--shoot-device]]
+    python examples/Lorenz96_D20/Lorenz96_anneal.py [--seeds 1] [--nbeta 101] [--disc SimpsonHermite] [--predict 40] [--spread 40] [--track 40] [--lyapunov 4000] [--shoot [--shoot-device]]
 """
 import argparse
 import os
@@ -42,6 +44,10 @@ def main():
     ap.add_argument("--spread", type=int, default=0, metavar="N",
                     help="hold the last N observations back and print the last rung's forecast +- 2 sigma (linearised spread "
                          "under the Laplace posterior: Annealer.predict_spread) and the share of them inside the band")
+    ap.add_argument("--track", type=int, default=0, metavar="N",
+                    help="hold the last N observations back and carry the last rung's estimate through them with an ensemble "
+                         "Kalman filter on the device (Annealer.track): per seed the RMS error of the analysis mean against the "
+                         "held-back data on the observed and on the unobserved columns, beside that of predict() over the same steps")
     ap.add_argument("--lyapunov", type=int, default=0, metavar="N",
                     help="print lambda_1, the horizon 1 / lambda_1 in steps of dt_model, the Kaplan-Yorke dimension and the largest "
                          "conditional exponent at a few gains on the measured columns, over N model steps (a multiple of 4) from the "
@@ -77,17 +83,19 @@ def main():
     times_data = data[:, 0]
     dt_data = times_data[1] - times_data[0]
     N_data = len(times_data)
-    data = data[:, 1:][:, Lidx]
+    all_columns = data[:, 1:]
+    data = all_columns[:, Lidx]
     held_back = None
-    if args.predict > 0 and args.spread > 0 and args.predict != args.spread:
-        ap.error("--predict and --spread hold the same rows back: give them the same N")
-    hold = max(args.predict, args.spread)
+    if len(set(n for n in (args.predict, args.spread, args.track) if n > 0)) > 1:
+        ap.error("--predict, --spread and --track hold the same rows back: give them the same N")
+    hold = max(args.predict, args.spread, args.track)
     if hold > 0:
         # fit what comes before the last N rows (Simpson-Hermite needs an odd number of them); the last fitted row is
         # row 0 of what the forecast is compared with
         n_fit = N_data - hold
         first = 1 if (args.disc == "SimpsonHermite" and n_fit % 2 == 0) else 0
         held_back = data[n_fit - 1:]
+        held_back_all = all_columns[n_fit - 1:]
         data, times_data, N_data = data[first:n_fit], times_data[first:n_fit], n_fit - first
 
     # Initial path/parameter guesses (reference lines 49-68)
@@ -142,6 +150,26 @@ def main():
                 inside = np.mean(np.abs(held_back[n] - mean[b, n, Lidx]) <= band)
                 print("seed %d   lead %3d steps   x_0 = %8.4f +- %.4f   inside the band: %3.0f %%"
                       % (b, n, mean[b, n, 0], 2.0 * std[b, n, 0], 100.0 * inside))
+
+    if args.track > 0:
+        # rows 1 .. N of what was held back are the observations that arrive after the window (row 0 is the last fitted
+        # time); obs_var = 1 / RM.  The file holds every column, so the unobserved ones can be scored too
+        tr = anneal1.track(held_back[1:], members=32, inflation=1.05)
+        lost = np.isnan(tr["mean_forecast"][..., 0, 0])                    # (NaN from row 0 on: no initial ensemble)
+        if np.any(lost):
+            print("\n(the exact Hessian is not positive definite at %d of %d seeds: members from the Gauss-Newton part)"
+                  % (int(np.sum(lost)), lost.size))
+            tr = anneal1.track(held_back[1:], members=32, inflation=1.05, gauss_newton=True)
+        fc = anneal1.predict(args.track, beta=-1).reshape(-1, args.track + 1, D)[:, 1:]
+        mean = tr["mean"].reshape(-1, args.track, D)
+        un = [i for i in range(D) if i not in Lidx]
+        rms = lambda m, cols: np.sqrt(np.mean((m[:, cols] - held_back_all[1:][:, cols]) ** 2))
+        print("\n%d held-back rows tracked from the last rung's estimate, 32 members (Annealer.track); RMS error against the data "
+              "(noise 0.5 in it)" % args.track)
+        for b in range(mean.shape[0]):
+            print("seed %d   status %d   observed columns: filter %.3f  predict() %.3f   unobserved columns: filter %.3f  predict() %.3f   k = %.3f +- %.3f"
+                  % (b, np.ravel(tr["status"])[b], rms(mean[b], Lidx), rms(fc[b], Lidx), rms(mean[b], un), rms(fc[b], un),
+                     tr["params"].reshape(-1, args.track, 1)[b, -1, 0], tr["params_std"].reshape(-1, args.track, 1)[b, -1, 0]))
 
     if args.lyapunov > 0:
         # finite-time exponents of the estimated model (discrete RK4 map) from the estimate; the first tenth of the steps

@@ -351,6 +351,30 @@ int va_lyapunov(va_handle h, const double *x0, const double *p, const double *Q0
                 double t0, int32_t n_steps, int32_t substeps, int32_t qr_every, int32_t n_skip, const double *stim,
                 double *logsum, double *x_end, double *Q_end, double *trace, int32_t *status);
 
+/* Track new data from the estimates: the ensemble Kalman filter of the handle's model on the device (csrc/va_enkf.h).  T
+ * points of M members each; for observation row k = 0 .. n_obs - 1 every member moves obs_every model steps as va_predict
+ * moves a trajectory (each with its own parameter vector), the forecast mean and standard deviation of the D + NQ augmented
+ * variables z = (x, p[est]) are recorded (mean in member order, variance over M - 1), the members are inflated about their
+ * mean (z = mean + inflation (z - mean); skipped exactly at 1), the observations of the row are assimilated one after the
+ * other by the serial ensemble square-root filter (Whitaker & Hamill 2002; a NaN is a missing observation), and the analysis
+ * mean and standard deviation are recorded.
+ *   x0 [T][M][D], p [T][M][NP] full vectors; est [NQ] the positions in p that the filter updates (NQ = 0: states only; the
+ *   other entries stay as given); Y [T][n_obs][L] the handle's Lidx columns, row k at t0 + (k + 1) obs_every dt_model;
+ *   obs_var [L]; stim as va_predict's, n_obs obs_every + 1 rows
+ *   mean_f, sd_f, mean_a, sd_a [T][n_obs][D + NQ];  x_end [T][M][D], p_end [T][M][NP]: where a following call starts;
+ *   status [T]: 0, or k + 1 of the first row at whose forecast some member of the point is not finite -- from that row on the
+ *           point's statistics are NaN, x_end / p_end hold what the arithmetic gave, the call still returns VA_OK.
+ * One workgroup per point: a point's bits do not depend on what shares its call.  Works on buffers of its own, chunked over
+ * points, like va_predict; the handle's resident state is left alone.  Bounds are not enforced on filtered parameters.
+ * VA_EINVAL (before the device is touched): what va_predict rejects; sizes below 1; est entries outside 0 .. NP-1 or
+ * repeated; an obs_var entry that is not positive and finite; inflation < 1.
+ * VA_EUNSUPPORTED (reason in va_last_error): network handles; generated models without a flat form; M < 2; M D > 2048; members,
+ * parameters and stimulus past 64 KiB of LDS; more stimulus columns than threads of a workgroup.  A module whose dense linear
+ * part was split off is carried (the members move through the predictor's own right-hand side). */
+int va_enkf(va_handle h, const double *x0, const double *p, const int32_t *est, int32_t NQ, const double *Y, const double *obs_var,
+            double inflation, int32_t T, int32_t M, double t0, int32_t n_obs, int32_t obs_every, int32_t substeps, const double *stim,
+            double *mean_f, double *sd_f, double *mean_a, double *sd_a, double *x_end, double *p_end, int32_t *status);
+
 /* Sample exp(-A(X, p)) at one rf_scale: B Hamiltonian Monte Carlo chains, one per seed of the handle, on the device
  * (csrc/va_hmc.h).  An iteration draws a momentum p = z / sqrt(minv), runs n_leap leapfrog steps of size
  * eps_it = eps[b] (1 + jitter (2 u - 1)) -- n_leap evaluations by the handle's own evaluation kernel, an element-wise launch

@@ -215,6 +215,9 @@ def lib():
     L.va_shoot.restype = C.c_int
     L.va_lyapunov.argtypes = [h, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double] + [C.c_int32] * 4 + [c_dp] * 5 + [c_ip]
     L.va_lyapunov.restype = C.c_int
+    L.va_enkf.argtypes = [h, c_dp, c_dp, c_ip, C.c_int32, c_dp, c_dp, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                          C.c_int32] + [c_dp] * 7 + [c_ip]
+    L.va_enkf.restype = C.c_int
     L.va_hess_vec.argtypes = [h, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, c_dp]
     L.va_hess_vec.restype = C.c_int
     L.va_blocktri_selinv.argtypes = [h, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [c_dp] * 9 + [c_ip]
@@ -258,7 +261,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_eval_grid", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_predict_adjoint", "va_shoot", "va_lyapunov", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_predict_adjoint", "va_shoot", "va_lyapunov", "va_enkf", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -692,6 +695,54 @@ class Problem(object):
                                   ptr(st), ptr(r["logsum"]), ptr(r["x_end"]), ptr(r["Q_end"]), ptr(r.get("trace")),
                                   r["status"].ctypes.data_as(c_ip)))
         r["exponents"] = r["logsum"] / ((n_qr - n_skip) * qr_every * self.desc.dt_model)
+        return r
+
+    def enkf(self, x0, p, Y, obs_var, obs_every=1, est=(), inflation=1.0, t0=0.0, substeps=1, stim=None):
+        """The ensemble Kalman filter of the model on the device (va_enkf; csrc/va_enkf.h): T points of M members, x0 (T, M, D)
+        with the members' full parameter vectors p (T, M, NP) ((M, NP) and (NP,) are repeated), observations Y (T, n_obs, L) or
+        (n_obs, L) for all points alike, of the handle's Lidx columns, NaN where one is missing; row k is at
+        t0 + (k + 1) obs_every dt_model.  obs_var (L,) or a scalar: the observation error variances; est: the positions in p the
+        filter updates; inflation >= 1 about the forecast mean.  Per row: obs_every model steps of every member (predict()'s
+        RK4), then the serial ensemble square-root analysis.  Returns a dict: mean_f, sd_f, mean_a, sd_a (T, n_obs, D + len(est))
+        of (x, p[est]) before and after each analysis; x_end (T, M, D), p_end (T, M, NP) to continue from; status (T,), 0 or
+        k + 1 of the first row whose forecast was not finite (the statistics are NaN from there; nothing raises)."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("enkf: a network handle has no differential equation to integrate")
+        D, NP, Ld = self.desc.D, self.desc.NP, self.desc.L
+        x0 = _f64(x0)
+        if x0.ndim == 2:
+            x0 = x0[None]
+        if x0.ndim != 3 or x0.shape[2] != D:
+            raise ValueError("enkf: x0 must have shape (T, M, D = %d), got %s" % (D, x0.shape))
+        T, M = x0.shape[:2]
+        p = _f64(p) if NP else np.zeros((T, M, 0))
+        if p.shape[-1:] != (NP,) or p.shape not in ((NP,), (M, NP), (T, M, NP)):
+            raise ValueError("enkf: p must have shape (%d, %d, NP = %d), (%d, %d) or (%d,), got %s" % (T, M, NP, M, NP, NP, p.shape))
+        p = np.ascontiguousarray(np.broadcast_to(p, (T, M, NP)))
+        Y = _f64(Y)
+        if Y.ndim == 2:
+            Y = np.broadcast_to(Y, (T,) + Y.shape)
+        if Y.ndim != 3 or Y.shape[0] != T or Y.shape[2] != Ld:
+            raise ValueError("enkf: Y must have shape (n_obs, L = %d) or (%d, n_obs, %d), got %s" % (Ld, T, Ld, Y.shape))
+        Y = np.ascontiguousarray(Y)
+        n_obs, obs_every, substeps = Y.shape[1], int(obs_every), int(substeps)
+        ov = np.asarray(obs_var, dtype=np.float64)
+        if ov.shape not in ((), (Ld,)):
+            raise ValueError("enkf: obs_var must be a scalar or have shape (L = %d,), got %s" % (Ld, ov.shape))
+        ov = np.ascontiguousarray(np.broadcast_to(ov, (Ld,)))
+        est = np.ascontiguousarray(np.asarray(est, dtype=np.int32).reshape(-1))
+        NV = D + est.size
+        st = None
+        if stim is not None:
+            st = _f64(stim).reshape(max(n_obs * obs_every, 0) + 1, -1)
+            if st.shape[1] != self.desc.n_stim and self.desc.n_stim:
+                raise ValueError("enkf: the stimulus must have %d rows of %d column(s)" % (n_obs * obs_every + 1, self.desc.n_stim))
+        r = dict(mean_f=np.empty((T, n_obs, NV)), sd_f=np.empty((T, n_obs, NV)), mean_a=np.empty((T, n_obs, NV)),
+                 sd_a=np.empty((T, n_obs, NV)), x_end=np.empty((T, M, D)), p_end=np.empty((T, M, NP)), status=np.zeros(T, dtype=np.int32))
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
+        check(self._L.va_enkf(self._h, ptr(x0), ptr(p), est.ctypes.data_as(c_ip) if est.size else None, est.size, ptr(Y), ptr(ov),
+                              float(inflation), T, M, float(t0), n_obs, obs_every, substeps, ptr(st), ptr(r["mean_f"]), ptr(r["sd_f"]),
+                              ptr(r["mean_a"]), ptr(r["sd_a"]), ptr(r["x_end"]), ptr(r["p_end"]), r["status"].ctypes.data_as(c_ip)))
         return r
 
     def hess_vec(self, XP, V, rf_scale, P=None, gauss_newton=False, tile_rows=0):

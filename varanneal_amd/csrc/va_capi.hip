@@ -42,6 +42,7 @@
 #include "va_predict_adj.h"
 #include "va_shoot.h"
 #include "va_lyap.h"
+#include "va_enkf.h"
 #include "va_hvp.h"
 #include "va_selinv.h"
 #include "va_hmc.h"
@@ -991,7 +992,7 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
         const int hb = hv(&u.hvp, (int)sizeof(HvpTable));
         if (hb != (int)sizeof(HvpTable) || u.hvp.hvp_bytes != (int)sizeof(HvpArgs) || u.hvp.tlm_bytes != (int)sizeof(PredictTlmArgs)
             || u.hvp.lyap_bytes != (int)sizeof(LyapArgs) || u.hvp.adj_bytes != (int)sizeof(PredictAdjArgs)
-            || u.hvp.shoot_bytes != (int)sizeof(ShootArgs)) {
+            || u.hvp.shoot_bytes != (int)sizeof(ShootArgs) || u.hvp.enkf_bytes != (int)sizeof(EnkfArgs)) {
             dlclose(u.dl);
             return fail(VA_EINVAL, "%s was built against different headers (HvpTable %d vs %zu bytes): rebuild it", path, hb, sizeof(HvpTable));
         }
@@ -1586,6 +1587,89 @@ int va_lyapunov(va_handle h, const double *x0, const double *p, const double *Q0
         HIPCHK(hipMemcpyAsync(x_end + (size_t)t1 * a.D, xe_d, sizeof(double) * n * a.D, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(Q_end + (size_t)t1 * K * a.D, qe_d, sizeof(double) * n * K * a.D, hipMemcpyDeviceToHost, h->stream));
         if (trace) HIPCHK(hipMemcpyAsync(trace + (size_t)t1 * n_qr * K, tr_d, sizeof(double) * n * n_qr * K, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(status + t1, stat_d, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
+    }
+    HIPCHK(hipGetLastError());
+    return VA_OK;
+}
+
+// The ensemble Kalman filter (va_enkf.h): T points of M members each, one workgroup per point, forecast and analysis
+// alternating inside one launch per chunk; the statistics of every observation row, the final members and their parameters
+// come back.  Chunked over points under a workspace limit; buffers of its own, like va_predict.
+int va_enkf(va_handle h, const double *x0, const double *p, const int32_t *est, int32_t NQ, const double *Y, const double *obs_var,
+            double inflation, int32_t T, int32_t M, double t0, int32_t n_obs, int32_t obs_every, int32_t substeps, const double *stim,
+            double *mean_f, double *sd_f, double *mean_a, double *sd_a, double *x_end, double *p_end, int32_t *status)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    if (!x0 || !p || !Y || !obs_var) return fail(VA_EINVAL, "va_enkf: x0 / p / Y / obs_var must not be NULL");
+    if (!mean_f || !sd_f || !mean_a || !sd_a || !x_end || !p_end || !status) return fail(VA_EINVAL, "va_enkf: the outputs must not be NULL");
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "a network handle has no differential equation to integrate");
+    const Dims &dm = h->dv.dm;
+    char why[192];
+    if (!enkf_check_args(T, M, dm.NPt, NQ, dm.L, n_obs, obs_every, substeps, est, obs_var, inflation, why, sizeof why))
+        return fail(VA_EINVAL, "va_enkf: %s", why);
+    const int nstim = h->dv.pp.nstim;
+    if ((int64_t)n_obs * obs_every * substeps > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_obs x obs_every x substeps does not fit 32-bit indexing");
+    const int n_steps = n_obs * obs_every;
+    if (nstim > 0 && !stim) return fail(VA_EINVAL, "the model takes a stimulus of %d column(s): pass its %d rows from t0 on", nstim, n_steps + 1);
+    if (nstim == 0 && stim) return fail(VA_EINVAL, "the model takes no stimulus, but one was passed");
+    // (a module whose dense linear part was split off is carried: the members move through predict_f, as va_predict's do)
+    if (!h->rt.predict || !h->rt_hvp.enkf)
+        return fail(VA_EUNSUPPORTED, "va_enkf: the model has no flat form f(x, i, p) to integrate (more than %d parameters: "
+                                     "its module carries the column-parameter form only)", RHS_BIG_NP);
+    EnkfArgs a;
+    a.T = T; a.D = dm.D; a.NP = dm.NPt; a.NQ = NQ; a.L = dm.L; a.M = M; a.nstim = nstim; a.n_obs = n_obs; a.obs_every = obs_every;
+    a.substeps = substeps; a.t0 = t0; a.dt = dm.dt; a.inflation = inflation;
+    const int NV = a.D + NQ;
+    const size_t per = enkf_point_doubles(a.D, a.NP, NQ, a.L, M, n_obs);
+    const long C = enkf_chunk_points(per, T);
+    if (C < 1)
+        return fail(VA_EUNSUPPORTED, "va_enkf: one point with %d observation rows takes %.1f MiB of device workspace, the limit is %zu MiB: "
+                                     "fewer rows per call (x_end / p_end continue a run)", n_obs, (double)per * 8.0 / 1048576.0,
+                    ENKF_WORKSPACE_BYTES >> 20);
+    if (!plan_enkf(a.D, C, M, a.NP, NQ, nstim, a.geo)) return fail(VA_EUNSUPPORTED, "va_enkf: D=%d M=%d: %s", a.D, M, a.geo.why);
+    HIPCHK(hipSetDevice(h->device));
+    // one allocation: [stim | obs_var | est | Lidx | x0 | p | Y | mean_f | sd_f | mean_a | sd_a | x_end | p_end | status], all
+    // but the first four for one chunk of C points
+    const size_t ns = (size_t)(n_steps + 1) * nstim, nov = a.L, nes = ((size_t)NQ + 1) / 2, nli = ((size_t)a.L + 1) / 2,
+                 nx = (size_t)C * M * a.D, np = (size_t)C * M * a.NP, ny = (size_t)C * n_obs * a.L, nst = (size_t)C * n_obs * NV;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (ns + nov + nes + nli + 2 * nx + 2 * np + ny + 4 * nst + (size_t)C + 1)));
+    struct Free { double *q; ~Free() { (void)hipFree(q); } } guard{buf};
+    double *st_d = buf, *ov_d = st_d + ns, *es_d = ov_d + nov, *li_d = es_d + nes, *x0_d = li_d + nli, *p_d = x0_d + nx, *y_d = p_d + np,
+           *mf_d = y_d + ny, *sf_d = mf_d + nst, *ma_d = sf_d + nst, *sa_d = ma_d + nst, *xe_d = sa_d + nst, *pe_d = xe_d + nx;
+    int *stat_d = (int *)(pe_d + np);
+    if (ns) HIPCHK(hipMemcpyAsync(st_d, stim, sizeof(double) * ns, hipMemcpyHostToDevice, h->stream));
+    if (a.L) {
+        HIPCHK(hipMemcpyAsync(ov_d, obs_var, sizeof(double) * a.L, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(li_d, h->lidx_user.data(), sizeof(int) * a.L, hipMemcpyHostToDevice, h->stream));
+    }
+    if (NQ) HIPCHK(hipMemcpyAsync(es_d, est, sizeof(int) * NQ, hipMemcpyHostToDevice, h->stream));
+    for (long t1 = 0; t1 < T; t1 += C) {
+        const long n = T - t1 < C ? T - t1 : C;
+        HIPCHK(hipMemcpyAsync(x0_d, x0 + (size_t)t1 * M * a.D, sizeof(double) * n * M * a.D, hipMemcpyHostToDevice, h->stream));
+        if (a.NP) HIPCHK(hipMemcpyAsync(p_d, p + (size_t)t1 * M * a.NP, sizeof(double) * n * M * a.NP, hipMemcpyHostToDevice, h->stream));
+        if (a.L) HIPCHK(hipMemcpyAsync(y_d, Y + (size_t)t1 * n_obs * a.L, sizeof(double) * n * n_obs * a.L, hipMemcpyHostToDevice, h->stream));
+        a.T = (int)n;
+        if (!plan_enkf(a.D, n, M, a.NP, NQ, nstim, a.geo)) {      // (the last chunk: the same plan on fewer workgroups)
+            (void)hipStreamSynchronize(h->stream);
+            return fail(VA_EUNSUPPORTED, "va_enkf: D=%d M=%d: %s", a.D, M, a.geo.why);
+        }
+        a.x0 = x0_d; a.p = p_d; a.Y = y_d; a.obs_var = ov_d; a.stim = ns ? st_d : nullptr; a.est = (const int *)es_d; a.Lidx = (const int *)li_d;
+        a.mean_f = mf_d; a.sd_f = sf_d; a.mean_a = ma_d; a.sd_a = sa_d; a.x_end = xe_d; a.p_end = pe_d; a.status = stat_d;
+        const hipError_t e = h->rt_hvp.enkf(a, h->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
+            return fail(VA_EHIP, "k_enkf launch: %s", hipGetErrorString(e));
+        }
+        const size_t so = (size_t)t1 * n_obs * NV, sb = sizeof(double) * n * n_obs * NV;
+        HIPCHK(hipMemcpyAsync(mean_f + so, mf_d, sb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(sd_f + so, sf_d, sb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(mean_a + so, ma_d, sb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(sd_a + so, sa_d, sb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(x_end + (size_t)t1 * M * a.D, xe_d, sizeof(double) * n * M * a.D, hipMemcpyDeviceToHost, h->stream));
+        if (a.NP) HIPCHK(hipMemcpyAsync(p_end + (size_t)t1 * M * a.NP, pe_d, sizeof(double) * n * M * a.NP, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(status + t1, stat_d, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
     }

@@ -147,22 +147,26 @@ struct RhsTable {
 void builtin_rhs_table(RhsTable &t);
 // The launcher slots of the kernels that call the right-hand side's derivatives along a direction (RHS::jvp and beyond): the
 // Hessian-vector kernel (va_hvp.h), the tangent-linear predictor (va_predict_tlm.h), the predictor's entry beside
-// `predict`, and the Lyapunov-spectrum kernel (va_lyap.h).  A table of its own beside RhsTable, whose layout modules and their checks already agree on: the built-in
+// `predict`, and the Lyapunov-spectrum kernel (va_lyap.h); and, because this is where new launchers go while RhsTable's layout
+// stays fixed, the ensemble Kalman filter (va_enkf.h), which calls RHS::f alone.  A table of its own beside RhsTable, whose layout modules and their checks already agree on: the built-in
 // fills one in va_kernels.hip (builtin_hvp_table), a generated module through a second entry point, va_user_hvp_table
 // (va_user_rhs.hip); a module without that entry point has no such kernels.
 struct PredictTlmArgs;
 struct LyapArgs;
 struct PredictAdjArgs;
 struct ShootArgs;
+struct EnkfArgs;
 struct HvpTable {
     int bytes, hvp_bytes, tlm_bytes, lyap_bytes;      // sizeof(HvpTable), sizeof(HvpArgs), sizeof(PredictTlmArgs), sizeof(LyapArgs)
     int adj_bytes;                                    // sizeof(PredictAdjArgs)
     int shoot_bytes;                                  // sizeof(ShootArgs)
+    int enkf_bytes;                                   // sizeof(EnkfArgs)
     hipError_t (*hvp)(const HvpArgs &, size_t lds_bytes, hipStream_t);      // or NULL
     hipError_t (*predict_tlm)(const PredictTlmArgs &, hipStream_t);         // or NULL
     hipError_t (*lyap)(const LyapArgs &, hipStream_t);                      // or NULL
     hipError_t (*predict_adj)(const PredictAdjArgs &, hipStream_t);         // the adjoint predictor (va_predict_adj.h), or NULL
     hipError_t (*shoot)(const ShootArgs &, hipStream_t);                    // the shooting kernel (va_shoot.h), or NULL
+    hipError_t (*enkf)(const EnkfArgs &, hipStream_t);                      // the ensemble Kalman filter (va_enkf.h), or NULL
 };
 void builtin_hvp_table(HvpTable &t);
 

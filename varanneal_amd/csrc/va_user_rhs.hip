@@ -21,6 +21,7 @@
 #include "va_predict_adj.h"
 #include "va_shoot.h"
 #include "va_lyap.h"
+#include "va_enkf.h"
 #include "va_hvp.h"
 
 #ifndef VA_USER_RHS_HEADER
@@ -72,11 +73,14 @@ template <class R> void fill_table(va::RhsTable &t)
     if constexpr (va::seed_kernel_exists<R>()) t.seed = va::seed_op<R>;
 }
 // the Hessian-vector kernel, the tangent-linear predictor, its adjoint and the Lyapunov-spectrum kernel: derivatives of the element-wise
-// part only (a split-off linear part would need products of its own), and only where a flat struct exists
+// part only (a split-off linear part would need products of its own), and only where a flat struct exists.  The ensemble
+// Kalman filter calls f alone, through predict_f as the predictor does: a split-off linear part is carried there
 template <class R> void fill_hvp_table(va::HvpTable &t)
 {
     t = va::HvpTable{(int)sizeof(va::HvpTable), (int)sizeof(va::HvpArgs), (int)sizeof(va::PredictTlmArgs), (int)sizeof(va::LyapArgs),
-                     (int)sizeof(va::PredictAdjArgs), (int)sizeof(va::ShootArgs), nullptr, nullptr, nullptr, nullptr, nullptr};
+                     (int)sizeof(va::PredictAdjArgs), (int)sizeof(va::ShootArgs), (int)sizeof(va::EnkfArgs), nullptr, nullptr, nullptr,
+                     nullptr, nullptr, nullptr};
+    if constexpr (va::rhs_flat<R>::value) t.enkf = va::launch_enkf<R, R::D>;
     if constexpr (va::rhs_flat<R>::value && !va::rhs_linear<R>::value) {
         t.hvp = va::launch_hvp<R>; t.predict_tlm = va::launch_predict_tlm<R, R::D>;
         t.predict_adj = va::launch_predict_adj<R, R::D>;

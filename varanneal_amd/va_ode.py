@@ -717,6 +717,33 @@ class Annealer(LadderAnnealer):
         (nbeta_sel, N, D) or (B_sel, nbeta_sel, N, D); NaN where the Hessian is not positive definite."""
         return np.sqrt(self.laplace(beta=beta, seeds=seeds, gauss_newton=gauss_newton)["state_var"])
 
+    def _laplace_factor(self, beta, seeds, gauss_newton):
+        """(seed indices, rung indices, status (npts,), F (npts, D + NPest, D + NPest)): one laplace(full=True) call gives the joint
+        covariance Sigma_0 of the last fitted state and the estimated parameters of every selected point (the last time row's
+        blocks of state_cov and state_param_cov, and param_cov); F is its lower Cholesky factor (host), zeros where there is
+        none: status is laplace()'s, or -2 where Sigma_0 has no factor."""
+        lap = self.laplace(beta=beta, seeds=seeds, gauss_newton=gauss_newton, full=True)
+        sb, kb = self._select(beta, seeds)
+        N, D, NPe = self.N_model, self.D, self.NPest
+        npts, nw = len(sb) * len(kb), D + NPe
+        status = np.array(lap["status"], dtype=np.int32).reshape(npts)
+        Sxx = lap["state_cov"].reshape(npts, N, D, D)[:, N - 1]
+        Spx = lap["state_param_cov"].reshape(npts, NPe, N, D)[:, :, N - 1]
+        Spp = lap["param_cov"].reshape(npts, NPe, NPe)
+        F = np.zeros((npts, nw, nw))
+        for j in range(npts):
+            if status[j] != 0:
+                continue
+            S0 = np.empty((nw, nw))
+            S0[:D, :D], S0[D:, :D], S0[:D, D:], S0[D:, D:] = Sxx[j], Spx[j], Spx[j].T, Spp[j]
+            try:
+                if not np.all(np.isfinite(S0)):
+                    raise np.linalg.LinAlgError("not finite")
+                F[j] = np.linalg.cholesky(S0)
+            except np.linalg.LinAlgError:
+                status[j] = -2
+        return sb, kb, status, F
+
     def predict_spread(self, n_steps, beta=None, seeds=None, substeps=1, every=1, stim=None, gauss_newton=False, full=False):
         """The forecast of predict() with its error bar: the LINEARISED spread of the model forecast under the Laplace
         posterior of every selected (seed, rung).  One laplace(full=True) call gives the joint covariance Sigma_0 of the
@@ -738,26 +765,10 @@ class Annealer(LadderAnnealer):
         added, so held-back data scatter around the band by their own error as well.  Refusals as laplace(): before
         anneal() ValueError; time-dependent parameters, states wider than 64 (32 with Simpson-Hermite) or more than 32
         estimated parameters NotImplementedError."""
-        lap = self.laplace(beta=beta, seeds=seeds, gauss_newton=gauss_newton, full=True)
-        sb, kb = self._select(beta, seeds)
+        sb, kb, status, F = self._laplace_factor(beta, seeds, gauss_newton)
         N, D, NP, NPe, NX = self.N_model, self.D, self.NP, self.NPest, self._NX
         npts, nw = len(sb) * len(kb), D + NPe
-        status = np.array(lap["status"], dtype=np.int32).reshape(npts)
-        Sxx = lap["state_cov"].reshape(npts, N, D, D)[:, N - 1]
-        Spx = lap["state_param_cov"].reshape(npts, NPe, N, D)[:, :, N - 1]
-        Spp = lap["param_cov"].reshape(npts, NPe, NPe)
-        V0 = np.zeros((npts, nw, nw))                                    # direction c of point j: column c of the factor
-        for j in range(npts):
-            if status[j] != 0:
-                continue
-            S0 = np.empty((nw, nw))
-            S0[:D, :D], S0[D:, :D], S0[:D, D:], S0[D:, D:] = Sxx[j], Spx[j], Spx[j].T, Spp[j]
-            try:
-                if not np.all(np.isfinite(S0)):
-                    raise np.linalg.LinAlgError("not finite")
-                V0[j] = np.linalg.cholesky(S0).T
-            except np.linalg.LinAlgError:
-                status[j] = -2
+        V0 = np.ascontiguousarray(F.transpose(0, 2, 1))                  # direction c of point j: column c of the factor
         rows = self._mp[sb][:, kb].reshape(npts, -1)
         r = self._pb.predict_tangent(rows[:, (N - 1) * D:N * D], rows[:, NX:], V0, n_steps, t0=float(self.t_model[-1]),
                                      substeps=substeps, every=every, stim=stim, want=("var", "cov") if full else ("var",))
@@ -979,6 +990,115 @@ class Annealer(LadderAnnealer):
         lead = (len(sb), len(kb)) if self._batched else (len(kb),)
         members = out.reshape(lead + (S, out.shape[1], D))
         return dict(members=members, quantiles=np.quantile(members, q, axis=len(lead)))
+
+    # ------------------------------------------------------------------ tracking new data: the ensemble Kalman filter
+    def _track_obs_var(self, obs_var):
+        L = self.L
+        if obs_var is None:
+            if np.ndim(self.RM) == 3:
+                raise ValueError("track: full RM matrices say nothing about one variance per observed column: pass obs_var")
+            if isinstance(self.RM, np.ndarray):
+                if np.any(self.RM != self.RM[:1]):
+                    raise ValueError("track: RM changes along the data window: pass obs_var for the rows to come")
+                return 1.0 / np.array(self.RM[0], dtype=np.float64)
+            return np.full(L, 1.0 / float(self.RM))
+        ov = np.asarray(obs_var, dtype=np.float64)
+        if ov.shape not in ((), (L,)) or not np.all(np.isfinite(ov)) or np.any(ov <= 0):
+            raise ValueError("track: obs_var is a positive finite number, or L = %d of them" % L)
+        return np.ascontiguousarray(np.broadcast_to(ov, (L,)))
+
+    def track(self, Y_future, obs_every=1, members=32, samples=None, obs_var=None, inflation=1.0, substeps=1, beta=-1, seeds=None,
+              stim=None, estimate_params=True, seed=0, gauss_newton=False):
+        """Carry the estimate and its uncertainty through observations that arrive AFTER the fitted window (after anneal()):
+        an ensemble Kalman filter on the device (csrc/va_enkf.h), all selected (seed, rung)s in ONE call.  Per observation
+        row every member moves obs_every steps of dt_model by predict()'s RK4 (dt_model / substeps), then the row's
+        observations are assimilated one after the other by the serial ensemble square-root filter (Whitaker & Hamill 2002).
+          Y_future   (n_obs, L), the Lidx columns; row k is at t_model[-1] + (k + 1) obs_every dt_model -- row 0 is NOT the last
+                     fitted time, unlike prediction_error's.  NaN: a missing observation.  Every selected point gets the same data.
+          members    M: the initial ensemble is drawn from the Laplace posterior -- one laplace(full=True) call gives the joint
+                     covariance of the last state and the estimated parameters, as predict_spread() assembles it; member m =
+                     estimate + (its Cholesky factor) . normals, the normals from the counter-based generator of sample()
+                     (_capi.hmc_noise(seed, chain = point index, iteration 0)).  A point whose covariance has no factor keeps
+                     predict_spread()'s status (-2, or laplace()'s own) and NaN outputs; nothing raises.
+          samples    a sample() result (keep=None) instead: its kept x_last / params are the members (predict_ensemble()'s
+                     bookkeeping); beta / seeds / members / seed are then not used
+          obs_var    (L,) or a number: the observation error variance; None: 1 / RM per observed column for a scalar or
+                     per-column RM (RM = 1 / sigma^2, the convention of the reference's examples).  RM arrays that change
+                     along the window and full RM matrices need an explicit obs_var (ValueError)
+          inflation  >= 1: every member's distance from the forecast mean is multiplied by it before each analysis
+          estimate_params  False: states only; the parameters stay as the members have them
+          stim       (n_obs obs_every + 1, n_stim), from t_model[-1] on, as predict()
+        Returns a dict, leading axes as predict():
+          mean, std (..., n_obs, D)                     the analysis mean and standard deviation after every row
+          mean_forecast, std_forecast (..., n_obs, D)   the same before the row was assimilated
+          params, params_std (..., n_obs, NPest)        the analysis statistics of the estimated parameters
+          innovation (..., n_obs, L)                    Y_future - mean_forecast[..., Lidx]
+          x_end (..., M, D), p_end (..., M, NP)         the members after the last row (to continue from)
+          status (...)   0; k + 1: row k's forecast was not finite (NaN from there on).  A point without an initial ensemble
+                         has predict_spread()'s status (-2, or laplace()'s own, which is positive inside the path) and NaN in
+                         every row, row 0 included
+          seeds, rungs   the selection
+        Bounds are NOT enforced on filtered states or parameters.  Not built: localisation, a full R, adaptive inflation.
+        Time-dependent parameters: NotImplementedError."""
+        if self._pb is None or not getattr(self, "initalized", False):
+            raise ValueError("track() works after anneal() / anneal_init()")
+        if self._tdp:
+            raise NotImplementedError("track: time-dependent parameters are not carried")
+        Yf = np.asarray(Y_future, dtype=np.float64)
+        if Yf.ndim != 2 or Yf.shape[0] < 1 or Yf.shape[1] != self.L:
+            raise ValueError("Y_future must have shape (n_obs >= 1, L = %d), got %s" % (self.L, Yf.shape))
+        ov = self._track_obs_var(obs_var)
+        if not float(inflation) >= 1.0:
+            raise ValueError("track: inflation is at least 1")
+        D, NP, NPe, NX, N = self.D, self.NP, self.NPest, self._NX, self.N_model
+        est = list(self.Pidx) if estimate_params else []
+        if samples is not None:
+            if "x_last" not in samples:
+                raise ValueError("track needs a sample() result with keep=None (x_last and params)")
+            sb, kb = samples["seeds"], samples["rungs"]
+            npts = len(sb) * len(kb)
+            x0 = np.asarray(samples["x_last"], dtype=np.float64).reshape(npts, -1, D)
+            M = x0.shape[1]
+            p = np.repeat(self._mp[sb][:, kb][:, :, None, NX:], M, axis=2).reshape(npts, M, NP)
+            if NPe:
+                p[..., self.Pidx] = np.asarray(samples["params"]).reshape(npts, M, NPe)
+            status0 = np.zeros(npts, dtype=np.int32)
+        else:
+            M = int(members)
+            if M < 2:
+                raise ValueError("track: an ensemble has at least 2 members")
+            sb, kb, status0, F = self._laplace_factor(beta, seeds, gauss_newton)
+            npts, nw = len(sb) * len(kb), D + NPe
+            rows = self._mp[sb][:, kb].reshape(npts, -1)
+            x0 = np.repeat(rows[:, None, (N - 1) * D:N * D], M, axis=1)
+            p = np.repeat(rows[:, None, NX:], M, axis=1)
+            for j in range(npts):
+                if status0[j] != 0:
+                    continue
+                z = _capi.hmc_noise(seed, j, 0, M * nw)[1].reshape(M, nw)
+                dz = np.dot(z, F[j].T)
+                x0[j] += dz[:, :D]
+                if NPe:
+                    p[j][:, self.Pidx] += dz[:, D:]
+        r = self._pb.enkf(np.ascontiguousarray(x0), np.ascontiguousarray(p), Yf, ov, obs_every=int(obs_every), est=est,
+                          inflation=float(inflation), t0=float(self.t_model[-1]), substeps=substeps, stim=stim)
+        lead = (len(sb), len(kb)) if self._batched else (len(kb),)
+        status = np.where(status0 != 0, status0, np.asarray(r["status"], dtype=np.int32))
+        bad = status0 != 0
+        n_obs, nq = Yf.shape[0], len(est)
+        stat = {k: np.array(r[k]) for k in ("mean_f", "sd_f", "mean_a", "sd_a")}
+        for v in stat.values():
+            v[bad] = np.nan
+        x_end, p_end = np.array(r["x_end"]), np.array(r["p_end"])
+        x_end[bad] = np.nan
+        p_end[bad] = np.nan
+        par = lambda a: a[..., D:] if nq else np.empty((npts, n_obs, 0))
+        out = dict(mean=stat["mean_a"][..., :D], std=stat["sd_a"][..., :D], mean_forecast=stat["mean_f"][..., :D],
+                   std_forecast=stat["sd_f"][..., :D], params=par(stat["mean_a"]), params_std=par(stat["sd_a"]),
+                   innovation=Yf - stat["mean_f"][..., self.Lidx], x_end=x_end, p_end=p_end, status=status)
+        out = {k: np.ascontiguousarray(v).reshape(lead + v.shape[1:]) for k, v in out.items()}
+        out["seeds"], out["rungs"] = sb, kb
+        return out
 
     def me_gaussian(self, X):
         """Measurement error of a path (va_ode.py:138-158); X may omit the parameters."""
