@@ -8,7 +8,10 @@ differentiates it and compiles f, J^T v and (df/dp)^T v for gfx950 on first use.
 tutorial's voltage recording is not shipped with the reference: a twin experiment is
 integrated here instead.
 
-    python examples/NaKL/NaKL_anneal.py [--nbeta 40] [--N 501]
+    python examples/NaKL/NaKL_anneal.py [--nbeta 40] [--N 501] [--sample 200]
+
+--sample N draws N states per chain at the last rung inside the bounds (Annealer.sample through the box sampler,
+csrc/va_hmc_box.h) and prints every parameter as mean +- std beside its true value.
 """
 import argparse
 import os
@@ -63,6 +66,7 @@ def main():
     ap.add_argument("--nbeta", type=int, default=40)
     ap.add_argument("--N", type=int, default=501)
     ap.add_argument("--out", default=".")
+    ap.add_argument("--sample", type=int, default=0, help="posterior samples per chain at the last rung (0: none)")
     args = ap.parse_args()
     dt = 0.02
     t, Iext, Y, truth = twin_data(args.N, dt)
@@ -86,6 +90,16 @@ def main():
     anneal1.save_paths(os.path.join(args.out, "paths.npy"))
     anneal1.save_params(os.path.join(args.out, "params.npy"))
     anneal1.save_action_errors(os.path.join(args.out, "action_errors.npy"))
+    if args.sample > 0:
+        # the chains run in an unconstrained z with x = T(z): every draw lies inside XB / PB.  Masses of z from laplace()
+        # where it has a factor; 100 warm-up iterations in blocks of 25 set the step by the acceptance rate.
+        r = anneal1.sample(args.sample, beta=-1, n_leap=10, warmup=100, thin=2, seed=1)
+        print("\nsampling at beta = %d: acceptance %.2f, %d divergent, %d start entries pulled off a bound%s"
+              % (args.nbeta - 1, float(np.mean(r["accept_rate"])), int(np.sum(r["n_divergent"])), int(np.sum(r["n_pulled_in"])),
+                 "" if r["mass_note"][0] is None else " (" + r["mass_note"][0] + ")"))
+        mean, std = np.asarray(r["mean"]).reshape(-1)[-18:], np.asarray(r["std"]).reshape(-1)[-18:]
+        for i in range(18):
+            print("  p[%2d] = %10.4f +- %-10.4f (true %8.3f, bounds [%g, %g])" % (i, mean[i], std[i], P_TRUE[i], PB[i][0], PB[i][1]))
 
 
 if __name__ == "__main__":

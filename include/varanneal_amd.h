@@ -393,11 +393,30 @@ int va_enkf(va_handle h, const double *x0, const double *p, const int32_t *est, 
  * (B (n_iter n_leap + 1)) are counted as va_action_grad's.  Plain launches on the handle's stream.
  * VA_EINVAL: n_iter, n_leap or thin < 1; an eps or minv entry not positive and finite; jitter outside [0, 1); a keep_idx
  * outside [0, n_var); a minv_n that is neither n_var nor B * n_var.
- * VA_EUNSUPPORTED: handles with box bounds, network handles. */
+ * VA_EUNSUPPORTED: handles with box bounds (va_hmc_box samples those), network handles. */
 int va_hmc(va_handle h, double *XP, int64_t ld, int32_t mem, double rf_scale, int32_t n_iter, int32_t n_leap, const double *eps,
            double jitter, const double *minv, int64_t minv_n, uint64_t seed, const double *noise, int32_t thin,
            const int64_t *keep_idx, int32_t n_keep_idx, double *mean, double *var, double *A_trace, double *dH, int32_t *accepted,
            int32_t *n_divergent, double *kept);
+/* va_hmc for box-bounded problems (csrc/va_hmc_box.h): the chain runs in an unconstrained z with x = T(z) element by
+ * element (T algebraic: + - * / sqrt), on the target U(z) = A(T(z)) - sum log|T'(z)|, so the x of its states follow exp(-A)
+ * restricted to the box.  va_hmc's arguments and outputs, which speak of x (statistics, kept columns, A_trace), plus:
+ *   lower, upper [n_var] (-/+HUGE_VAL: no bound), shared by the chains; both NULL: the handle's own bounds.  Bounds may be
+ *        passed on a handle created without any -- the sampler does not care which evaluation kernel runs.
+ *   Z0 NULL: the chains start at XP, inverted on the host; or [B][n_var] the start in z (XP is then only written)
+ *   Z_out NULL or [B][n_var]: the final z -- pass it as the next call's Z0 to continue a chain without re-inverting x
+ *   minv is the inverse mass of z; dH includes the log-Jacobian terms.
+ * The tails of T are polynomial (|dx/dz| ~ 1/z^2 for one-sided, 1/|z|^3 for two-sided bounds): good for bounds used as
+ * guards, weak where the posterior piles up on a bound.
+ * VA_EINVAL (naming the entry): lower[i] >= upper[i] or NaN; a start not strictly inside its box; a Z0 entry not finite;
+ * everything va_hmc rejects.  VA_EUNSUPPORTED: network handles; no finite bound from either source. */
+int va_hmc_box(va_handle h, double *XP, int64_t ld, int32_t mem, double rf_scale, int32_t n_iter, int32_t n_leap, const double *eps,
+               double jitter, const double *minv, int64_t minv_n, uint64_t seed, const double *noise, int32_t thin,
+               const int64_t *keep_idx, int32_t n_keep_idx, const double *lower, const double *upper, const double *Z0, double *Z_out,
+               double *mean, double *var, double *A_trace, double *dH, int32_t *accepted, int32_t *n_divergent, double *kept);
+/* The map of va_hmc_box as the current device computes it, entry by entry over a table: x = T(z), dx = dx/dz,
+ * dlj = d log|dx/dz| / dz, lj = log|dx/dz| [n].  HOST arrays.  Needs no handle. */
+int va_hmc_box_map(int64_t n, const double *lower, const double *upper, const double *z, double *x, double *dx, double *dlj, double *lj);
 /* Exactly what va_hmc's kernels draw for (seed, chain, iteration), computed on the current device: words [(n + 1)*4] the
  * generator's four words for each of the n elements and for the extra stream, normals [n], uniforms [2] (accept, jitter).
  * HOST arrays, any may be NULL.  Needs no handle. */

@@ -3,6 +3,7 @@
 NumPy chain (tests/_hmc_ref.py) driven by Problem.action_grad, which moves every path over PCIe twice per step.
 
     python tools/hmc_timed.py [--out profiles/hmc_timed.json] [--reps 7] [--iters 400] [--leap 10]
+    python tools/hmc_timed.py --box     the box sampler's step (va_hmc_box, a box on every entry) beside va_hmc's, same handle
 
 Like with like.  The sampler launches plainly, so the evaluation beside it is eval_timed with graph replay switched off
 (eval_plain_us: HIP events around plain launches of the evaluation kernel alone); the sampler's step is the MARGINAL one,
@@ -36,6 +37,40 @@ def timed_s(f, reps):
     return float(np.median(ts)), float(np.min(ts)), float(np.max(ts))
 
 
+def box_main(args):
+    """--box: the marginal leapfrog step (calls with n_leap and n_leap - 1 steps, difference / iters) of hmc_box with a
+    two-sided box on every entry, beside the same measurement of hmc, same handle, same run, same step size"""
+    D, N, B, rf = 20, 161, args.chains, 1.5 ** 10
+    t, Y, _, Lidx = twin.make_twin(D, N)
+    XP = np.empty((B, N * D + 1)); P = np.empty((B, 1))
+    for b in range(B):
+        X0, P0 = twin.initial_guess(N, D, b, Y, Lidx)
+        XP[b, :-1] = X0.ravel(); XP[b, -1] = P0[0]; P[b] = P0
+    bounds = [(-20.0, 20.0)] * (N * D) + [(0.5, 20.0)]
+    XP = np.clip(XP, [b[0] + 0.5 for b in bounds], [b[1] - 0.5 for b in bounds])
+    steps = args.iters * args.leap
+    doc = dict(what="va_hmc_box with a two-sided box on every entry beside va_hmc on the same handle in the same run, us per leapfrog "
+                    "step: marginal (calls with n_leap and n_leap - 1 steps per iteration, difference / iters) and whole call / steps, "
+                    "wall clock, median [min, max]; no threshold",
+               D=D, N=N, chains=B, n_var=N * D + 1, iters=args.iters, n_leap=args.leap, reps=args.reps, bounds="(-20, 20) states, (0.5, 20) parameter")
+    with _capi.Problem(B, D, N, Y, Lidx, twin.DT, 4.0, 4e-6, P, [0], disc="trapezoid") as pb:
+        doc["eval_kernel"] = pb.info()["eval_kernel"]
+        runs = dict(hmc=lambda leap: pb.hmc(XP, rf, args.iters, leap, 0.02, jitter=0.1, seed=1),
+                    hmc_box=lambda leap: pb.hmc_box(XP, rf, args.iters, leap, 0.02, bounds=bounds, jitter=0.1, seed=1))
+        for name, run in runs.items():
+            full, less = timed_s(lambda: run(args.leap), args.reps), timed_s(lambda: run(args.leap - 1), args.reps)
+            doc[name + "_call_step_us"] = [1e6 * v / steps for v in full]
+            doc[name + "_marginal_step_us"] = 1e6 * (full[0] - less[0]) / args.iters
+            doc[name + "_call_ms"], doc[name + "_call_one_step_less_ms"] = [1e3 * v for v in full], [1e3 * v for v in less]
+            doc[name + "_accept_rate"] = float(run(args.leap)["accepted"].mean())
+    doc["box_marginal_over_hmc_marginal"] = doc["hmc_box_marginal_step_us"] / doc["hmc_marginal_step_us"]
+    txt = json.dumps(doc, indent=1)
+    print(txt)
+    with open(args.out or os.path.join(ROOT, "profiles", "hmc_box_timed.json"), "w") as fh:
+        fh.write(txt + "\n")
+    return 0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -44,7 +79,11 @@ if __name__ == "__main__":
     ap.add_argument("--leap", type=int, default=10)
     ap.add_argument("--chains", type=int, default=64)
     ap.add_argument("--numpy-iters", type=int, default=10)
+    ap.add_argument("--box", action="store_true", help="time va_hmc_box with a box on every entry beside va_hmc on the same handle "
+                                                       "(default --out profiles/hmc_box_timed.json)")
     args = ap.parse_args()
+    if args.box:
+        sys.exit(box_main(args))
     import _hmc_ref
     D, N, B, rf = 20, 161, args.chains, 1.5 ** 10
     t, Y, _, Lidx = twin.make_twin(D, N)

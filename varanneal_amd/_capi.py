@@ -227,6 +227,11 @@ def lib():
     L.va_hmc.argtypes = [h, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32, c_dp, C.c_double, c_dp, C.c_int64,
                          C.c_uint64, c_dp, C.c_int32, c_lp, C.c_int32, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip, c_dp]
     L.va_hmc.restype = C.c_int
+    L.va_hmc_box.argtypes = [h, C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32, c_dp, C.c_double, c_dp, C.c_int64,
+                             C.c_uint64, c_dp, C.c_int32, c_lp, C.c_int32, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip, c_dp]
+    L.va_hmc_box.restype = C.c_int
+    L.va_hmc_box_map.argtypes = [C.c_int64] + [c_dp] * 7
+    L.va_hmc_box_map.restype = C.c_int
     L.va_hmc_noise.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_uint32), c_dp, c_dp]
     L.va_hmc_noise.restype = C.c_int
     L.va_eval_timed.argtypes = [h, C.c_double, C.c_int32, C.POINTER(C.c_float)]
@@ -261,7 +266,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_eval_grid", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_predict_adjoint", "va_shoot", "va_lyapunov", "va_enkf", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_predict_adjoint", "va_shoot", "va_lyapunov", "va_enkf", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_box", "va_hmc_box_map", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -315,6 +320,17 @@ def hmc_noise(seed, chain, iteration, n):
     check(lib().va_hmc_noise(int(seed) & (2 ** 64 - 1), int(chain), int(iteration), n, words.ctypes.data_as(C.POINTER(C.c_uint32)),
                              normals.ctypes.data_as(c_dp), uniforms.ctypes.data_as(c_dp)))
     return words, normals, uniforms
+
+
+def hmc_box_map(lower, upper, z):
+    """The map of Problem.hmc_box entry by entry, from the device itself (va_hmc_box_map): lower, upper, z (n,) -- infinite
+    bounds mean none -- give (x, dx/dz, d log|dx/dz| / dz, log|dx/dz|), each (n,)."""
+    lo, hi, z = (np.ascontiguousarray(_f64(v).reshape(-1)) for v in (lower, upper, z))
+    if not lo.size == hi.size == z.size:
+        raise ValueError("hmc_box_map: lower, upper and z have one entry each per table row")
+    out = [np.empty(z.size) for _ in range(4)]
+    check(lib().va_hmc_box_map(z.size, *[a.ctypes.data_as(c_dp) for a in [lo, hi, z] + out]))
+    return tuple(out)
 
 
 _modules = {}
@@ -856,6 +872,49 @@ class Problem(object):
                              0 if minv is None else minv.size, int(seed) & (2 ** 64 - 1), ptr(noise), thin, keep.ctypes.data_as(c_lp),
                              keep.size, ptr(out["mean"]), ptr(out["var"]), ptr(out["A"]), ptr(out["dH"]),
                              out["accepted"].ctypes.data_as(c_ip), out["n_divergent"].ctypes.data_as(c_ip), ptr(out["kept"])))
+        return out
+
+    def hmc_box(self, XP, rf_scale, n_iter, n_leap, eps, bounds=None, z0=None, jitter=0.0, minv=None, seed=0, noise=None, thin=1,
+                keep_idx=None):
+        """hmc() for box-bounded problems (va_hmc_box; csrc/va_hmc_box.h): the chains run in an unconstrained z with
+        x = T(z) element by element, so every state lies inside its closed box and follows exp(-A) restricted to it.  bounds: one
+        (lo, hi) per entry of the path vector (None: no bound on that side), shared by the chains; None: the handle's own.
+        z0 (B, n_var): start in z instead of XP (the 'z' of an earlier result continues its chain without re-inverting
+        x); a start in XP must lie strictly inside its box.  minv is the inverse mass OF z.  Returns hmc's dict (all of
+        it about x) plus z (B, n_var), the final unconstrained state."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("hmc_box: network handles are not sampled (ODE handles only)")
+        XP = self._xp(XP).copy()
+        B, n = self.B, self.n_var
+        n_iter, n_leap, thin = int(n_iter), int(n_leap), int(thin)
+        eps = np.ascontiguousarray(np.broadcast_to(_f64(eps).reshape(-1), (B,)))
+        lo = hi = None
+        if bounds is not None:
+            if len(bounds) != n:
+                raise ValueError("hmc_box: bounds must have one (lo, hi) pair per entry of the path vector (%d), got %d" % (n, len(bounds)))
+            lo = np.array([-np.inf if b[0] is None else b[0] for b in bounds], dtype=np.float64)
+            hi = np.array([np.inf if b[1] is None else b[1] for b in bounds], dtype=np.float64)
+        if z0 is not None:
+            z0 = _f64(z0)
+            if z0.shape != (B, n):
+                raise ValueError("hmc_box: z0 must have shape (B, n_var) = (%d, %d), got %s" % (B, n, z0.shape))
+        if minv is not None:
+            minv = _f64(minv)
+            if minv.shape not in [(n,), (B, n)]:
+                raise ValueError("hmc_box: minv must have shape (n_var,) = (%d,) or (B, n_var) = (%d, %d), got %s" % (n, B, n, minv.shape))
+        if noise is not None:
+            noise = _f64(noise)
+            if noise.shape != (max(n_iter, 0), B, n + 2):
+                raise ValueError("hmc_box: noise must have shape (n_iter, B, n_var + 2) = (%d, %d, %d), got %s" % (n_iter, B, n + 2, noise.shape))
+        keep = np.ascontiguousarray(np.zeros(0) if keep_idx is None else keep_idx, dtype=np.int64).reshape(-1)
+        ni, nk = max(n_iter, 1), max(n_iter, 1) // max(thin, 1)
+        out = dict(x=XP, z=np.empty((B, n)), mean=np.empty((B, n)), var=np.empty((B, n)), A=np.empty((B, ni)), dH=np.empty((B, ni)),
+                   accepted=np.empty((B, ni), np.int32), n_divergent=np.empty(B, np.int32), kept=np.empty((B, nk, keep.size)))
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
+        check(self._L.va_hmc_box(self._h, XP.ctypes.data, n, MEM_HOST, float(rf_scale), n_iter, n_leap, ptr(eps), float(jitter), ptr(minv),
+                                 0 if minv is None else minv.size, int(seed) & (2 ** 64 - 1), ptr(noise), thin, keep.ctypes.data_as(c_lp),
+                                 keep.size, ptr(lo), ptr(hi), ptr(z0), ptr(out["z"]), ptr(out["mean"]), ptr(out["var"]), ptr(out["A"]),
+                                 ptr(out["dH"]), out["accepted"].ctypes.data_as(c_ip), out["n_divergent"].ctypes.data_as(c_ip), ptr(out["kept"])))
         return out
 
     def eval_timed_prepare(self, rf_scale, iters):

@@ -46,6 +46,7 @@
 #include "va_hvp.h"
 #include "va_selinv.h"
 #include "va_hmc.h"
+#include "va_hmc_box.h"
 
 using namespace va;
 
@@ -1690,7 +1691,7 @@ int va_hmc(va_handle h, double *XP, int64_t ld, int32_t mem, double rf_scale, in
     if (h->is_nnet) return fail(VA_EUNSUPPORTED, "va_hmc: network handles are not sampled (ODE handles only)");
     Dev &dv = h->dv;
     const Dims &dm = dv.dm;
-    if (dm.bounded) return fail(VA_EUNSUPPORTED, "va_hmc: the handle has box bounds; a reflecting sampler is not implemented");
+    if (dm.bounded) return fail(VA_EUNSUPPORTED, "va_hmc: the handle has box bounds; va_hmc_box samples them through a transform");
     const long n_var = dm.ND + dm.NPest, B = dm.B;
     char why[192];
     if (hmc_check_args(n_var, B, n_iter, n_leap, thin, eps, jitter, minv, (long)minv_n, keep_idx, n_keep_idx, why, sizeof why))
@@ -1783,6 +1784,188 @@ int va_hmc(va_handle h, double *XP, int64_t ld, int32_t mem, double rf_scale, in
         }
         if (n_divergent) n_divergent[b] = nd;
     }
+    return VA_OK;
+}
+
+// The sampler for box-bounded problems (va_hmc_box.h): va_hmc's call with the chain run in z, x = T(z) written into the
+// handle's paths before every evaluation.  Kinds, start check and T^-1 on the host (va_hmc_geo.h, hmc_box_inverse); the
+// start's x = T(z) too (IEEE + - * / sqrt: the bits the device's map gives), so the chain's first x is its z's own image.
+int va_hmc_box(va_handle h, double *XP, int64_t ld, int32_t mem, double rf_scale, int32_t n_iter, int32_t n_leap, const double *eps,
+               double jitter, const double *minv, int64_t minv_n, uint64_t seed, const double *noise, int32_t thin,
+               const int64_t *keep_idx, int32_t n_keep_idx, const double *lower, const double *upper, const double *Z0, double *Z_out,
+               double *mean, double *var, double *A_trace, double *dH, int32_t *accepted, int32_t *n_divergent, double *kept)
+{
+    TRY(check_xp(h, XP, ld, mem));
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "va_hmc_box: network handles are not sampled (ODE handles only)");
+    Dev &dv = h->dv;
+    const Dims &dm = dv.dm;
+    if ((lower != nullptr) != (upper != nullptr)) return fail(VA_EINVAL, "va_hmc_box: lower and upper come together");
+    if (!lower && !dm.bounded)
+        return fail(VA_EUNSUPPORTED, "va_hmc_box: no bounds: the handle has none and lower / upper are NULL (va_hmc samples unbounded problems)");
+    const long n_var = dm.ND + dm.NPest, B = dm.B;
+    char why[256];
+    if (hmc_check_args(n_var, B, n_iter, n_leap, thin, eps, jitter, minv, (long)minv_n, keep_idx, n_keep_idx, why, sizeof why))
+        return fail(VA_EINVAL, "va_hmc_box: %s", why);
+    if (!std::isfinite(rf_scale)) return fail(VA_EINVAL, "va_hmc_box: rf_scale is not finite");
+    HmcBoxArgs a = {};
+    if (!plan_hmc(n_var, B, a.h.geo, why, sizeof why)) return fail(VA_EUNSUPPORTED, "va_hmc_box: %s", why);
+    HIPCHK(hipSetDevice(h->device));
+    // bounds (the handle's own come back from its device tables), kinds, the start in x and in z
+    std::vector<double> lo_h((size_t)n_var), hi_h((size_t)n_var);
+    std::vector<int32_t> kind_h((size_t)n_var);
+    if (lower) {
+        for (long i = 0; i < n_var; ++i) { lo_h[i] = lower[i]; hi_h[i] = upper[i]; }
+    } else {
+        HIPCHK(hipMemcpyAsync(lo_h.data(), dv.pp.lo, sizeof(double) * n_var, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(hi_h.data(), dv.pp.hi, sizeof(double) * n_var, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    const long n_bounded = hmc_box_kinds(n_var, lo_h.data(), hi_h.data(), kind_h.data(), why, sizeof why);
+    if (n_bounded < 0) return fail(VA_EINVAL, "va_hmc_box: %s", why);
+    if (n_bounded == 0) return fail(VA_EUNSUPPORTED, "va_hmc_box: %s", why);
+    const size_t nvv = (size_t)B * n_var;
+    std::vector<double> x_h(nvv), z_h(nvv);
+    if (Z0) {
+        if (hmc_box_check_z(n_var, B, n_var, Z0, why, sizeof why)) return fail(VA_EINVAL, "va_hmc_box: %s", why);
+        for (size_t k = 0; k < nvv; ++k) z_h[k] = Z0[k];
+    } else {
+        if (mem == VA_MEM_DEVICE) {
+            HIPCHK(hipMemcpy2DAsync(x_h.data(), sizeof(double) * n_var, XP, sizeof(double) * ld, sizeof(double) * n_var, B, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+        } else {
+            for (long b = 0; b < B; ++b)
+                for (long i = 0; i < n_var; ++i) x_h[(size_t)b * n_var + i] = XP[(size_t)b * ld + i];
+        }
+        if (hmc_box_check_start(n_var, B, n_var, x_h.data(), lo_h.data(), hi_h.data(), why, sizeof why)) return fail(VA_EINVAL, "va_hmc_box: %s", why);
+        for (long b = 0; b < B; ++b)
+            for (long i = 0; i < n_var; ++i) {
+                const size_t k = (size_t)b * n_var + i;
+                z_h[k] = hmc_box_inverse(kind_h[i], lo_h[i], hi_h[i], x_h[k]);
+            }
+    }
+    for (long b = 0; b < B; ++b)
+        for (long i = 0; i < n_var; ++i) {
+            const size_t k = (size_t)b * n_var + i;
+            double dx, dlj, lj;
+            hmc_box_map(kind_h[i], lo_h[i], hi_h[i], z_h[k], &x_h[k], &dx, &dlj, &lj);
+        }
+    // the inverse mass of z and its square root (IEEE on the host)
+    const bool per_chain = minv && minv_n == B * n_var && B > 1;
+    const size_t nm = per_chain ? (size_t)B * n_var : (size_t)n_var;
+    std::vector<double> mh(nm, 1.0), sh(nm, 1.0), dh((size_t)B * n_iter);
+    if (minv) for (size_t i = 0; i < nm; ++i) { mh[i] = minv[i]; sh[i] = sqrt(minv[i]); }
+    // one allocation, zeroed: [save | p | xs | gs | z | zs | minv | sminv | eps | noise | A_cur | part | lpart | mean | m2 |
+    // A_trace | dH | kept | lo | hi | keep_idx (int64) | accepted (int32) | kind (int32)]
+    const size_t nv = (size_t)B * dm.ld, nn = noise ? (size_t)n_iter * B * (n_var + 2) : 0, nt = (size_t)B * n_iter,
+                 nk = (size_t)B * (n_iter / thin) * n_keep_idx, ns = (size_t)B * n_var, ng = (size_t)a.h.geo.grid;
+    const size_t total = 6 * nv + 2 * nm + B + nn + 2 * B + 4 * ng + 2 * ns + 2 * nt + nk + 2 * (size_t)n_var + (size_t)n_keep_idx +
+                         (nt + 1) / 2 + ((size_t)n_var + 1) / 2 + 1;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * total));
+    struct Free { double *q; hipStream_t s; ~Free() { (void)hipStreamSynchronize(s); (void)hipFree(q); } } guard{buf, h->stream};
+    HIPCHK(hipMemsetAsync(buf, 0, sizeof(double) * total, h->stream));
+    double *q = buf;
+    auto take = [&q](size_t n) { double *r = q; q += n; return r; };
+    HmcArgs &ha = a.h;
+    double *save = take(nv);
+    ha.p = take(nv); ha.xs = take(nv); ha.gs = take(nv); a.z = take(nv); a.zs = take(nv);
+    double *minv_d = take(nm), *sminv_d = take(nm), *eps_d = take(B), *noise_d = take(nn);
+    ha.A_cur = take(2 * B); ha.part = take(2 * ng); a.lpart = take(2 * ng); ha.mean = take(ns); ha.m2 = take(ns);
+    ha.A_trace = take(nt); ha.dH = take(nt); ha.kept = take(nk);
+    double *lo_d = take(n_var), *hi_d = take(n_var);
+    int64_t *keep_d = (int64_t *)take(n_keep_idx);
+    ha.accepted = (int32_t *)take((nt + 1) / 2);
+    int32_t *kind_d = (int32_t *)take(((size_t)n_var + 1) / 2);
+    HIPCHK(hipMemcpyAsync(minv_d, mh.data(), sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(sminv_d, sh.data(), sizeof(double) * nm, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(eps_d, eps, sizeof(double) * B, hipMemcpyHostToDevice, h->stream));
+    if (nn) HIPCHK(hipMemcpyAsync(noise_d, noise, sizeof(double) * nn, hipMemcpyHostToDevice, h->stream));
+    if (n_keep_idx) HIPCHK(hipMemcpyAsync(keep_d, keep_idx, sizeof(int64_t) * n_keep_idx, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(lo_d, lo_h.data(), sizeof(double) * n_var, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(hi_d, hi_h.data(), sizeof(double) * n_var, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(kind_d, kind_h.data(), sizeof(int32_t) * n_var, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpy2DAsync(a.z, sizeof(double) * dm.ld, z_h.data(), sizeof(double) * n_var, sizeof(double) * n_var, B, hipMemcpyHostToDevice, h->stream));
+    ha.x = dv.x; ha.g = dv.gt; ha.minv = minv_d; ha.sminv = sminv_d; ha.minv_stride = per_chain ? n_var : 0; ha.eps = eps_d; ha.jitter = jitter;
+    ha.noise = nn ? noise_d : nullptr; ha.k0 = (uint32_t)seed; ha.k1 = (uint32_t)(seed >> 32); ha.chain0 = 0u; ha.A_eval = dv.outA;
+    ha.keep_idx = keep_d; ha.n_keep = n_keep_idx; ha.ld = dm.ld; ha.n_var = n_var; ha.B = (int)B; ha.n_iter = n_iter; ha.thin = thin;
+    a.kind = kind_d; a.lo = lo_d; a.hi = hi_d;
+    HIPCHK(hipMemcpyAsync(save, dv.x, sizeof(double) * nv, hipMemcpyDeviceToDevice, h->stream));
+    // whatever ends the sampling from here on, the handle goes back to what it was (as va_hmc)
+    int64_t n_evals = 0;
+    auto leave = [&]() {
+        (void)hipMemcpyAsync(dv.x, save, sizeof(double) * nv, hipMemcpyDeviceToDevice, h->stream);
+        launch_init_states(dv, PH_IDLE, 1.0, h->stream);
+        h->timed_armed_rf = -1.0;
+        h->n_eval_launch += n_evals; h->n_seed_evals += n_evals * B; h->n_seed_evals_direct += n_evals * B;
+    };
+    if (int rc_in = copy_in(h, x_h.data(), n_var, VA_MEM_HOST)) { leave(); return rc_in; }
+    launch_init_states(dv, PH_START, rf_scale, h->stream);
+    h->timed_armed_rf = rf_scale;
+    run_eval(h, EPI_FINALIZE); ++n_evals;
+    hipError_t e = hipMemcpyAsync(ha.A_cur, dv.outA, sizeof(double) * B, hipMemcpyDeviceToDevice, h->stream);
+    for (int it = 0; it < n_iter && e == hipSuccess; ++it) {
+        ha.it = it;
+        e = launch_hmc_box(a, HMC_BEGIN, h->stream);
+        for (int l = 0; l < n_leap && e == hipSuccess; ++l) {
+            if (l) e = launch_hmc_box(a, HMC_MID, h->stream);
+            if (e == hipSuccess) { run_eval(h, EPI_FINALIZE); ++n_evals; e = hipGetLastError(); }
+        }
+        if (e == hipSuccess) e = launch_hmc_box(a, HMC_END, h->stream);
+        if (e == hipSuccess) e = launch_hmc_box(a, HMC_COMMIT, h->stream);
+    }
+    if (e != hipSuccess) {
+        leave();
+        return fail(VA_EHIP, "va_hmc_box launch: %s", hipGetErrorString(e));
+    }
+    int rc = copy_out(h, dv.x, XP, ld, mem);
+    leave();
+    if (rc) return rc;
+    if (Z_out) HIPCHK(hipMemcpy2DAsync(Z_out, sizeof(double) * n_var, a.z, sizeof(double) * dm.ld, sizeof(double) * n_var, B, hipMemcpyDeviceToHost, h->stream));
+    if (mean) HIPCHK(hipMemcpyAsync(mean, ha.mean, sizeof(double) * ns, hipMemcpyDeviceToHost, h->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, ha.m2, sizeof(double) * ns, hipMemcpyDeviceToHost, h->stream));
+    if (A_trace) HIPCHK(hipMemcpyAsync(A_trace, ha.A_trace, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(dh.data(), ha.dH, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
+    if (accepted) HIPCHK(hipMemcpyAsync(accepted, ha.accepted, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, h->stream));
+    if (kept && nk) HIPCHK(hipMemcpyAsync(kept, ha.kept, sizeof(double) * nk, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    if (var) for (size_t i = 0; i < ns; ++i) var[i] = n_iter > 1 ? var[i] / (double)(n_iter - 1) : 0.0;
+    for (long b = 0; b < B; ++b) {
+        int nd = 0;
+        for (int it = 0; it < n_iter; ++it) {
+            const double v = dh[(size_t)b * n_iter + it];
+            if (!std::isfinite(v)) ++nd;
+            if (dH) dH[(size_t)b * n_iter + it] = v;
+        }
+        if (n_divergent) n_divergent[b] = nd;
+    }
+    return VA_OK;
+}
+
+// hmc_box_map as the current device computes it, over a table of n entries (HOST arrays; lower / upper -/+HUGE_VAL: none).
+// Needs no handle.
+int va_hmc_box_map(int64_t n, const double *lower, const double *upper, const double *z, double *x, double *dx, double *dlj, double *lj)
+{
+    if (n < 1 || n > 2147483647LL || !lower || !upper || !z || !x || !dx || !dlj || !lj) return fail(VA_EINVAL, "va_hmc_box_map: n from 1 to 2^31 - 1 and no NULL array");
+    char why[256];
+    std::vector<int32_t> kind((size_t)n);
+    if (hmc_box_kinds((long)n, lower, upper, kind.data(), why, sizeof why) < 0) return fail(VA_EINVAL, "va_hmc_box_map: %s", why);
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (7 * (size_t)n + ((size_t)n + 1) / 2)));
+    struct Free { double *q; ~Free() { (void)hipDeviceSynchronize(); (void)hipFree(q); } } guard{buf};
+    double *lo_d = buf, *hi_d = buf + n, *z_d = buf + 2 * n, *out_d = buf + 3 * n;
+    int32_t *kind_d = (int32_t *)(buf + 7 * n);
+    HIPCHK(hipMemcpy(lo_d, lower, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(hi_d, upper, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(z_d, z, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(kind_d, kind.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    const hipError_t e = launch_hmc_box_map((long)n, kind_d, lo_d, hi_d, z_d, out_d, out_d + n, out_d + 2 * n, out_d + 3 * n, nullptr);
+    if (e != hipSuccess) return fail(VA_EHIP, "k_hmc_box_map launch: %s", hipGetErrorString(e));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(x, out_d, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dx, out_d + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dlj, out_d + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lj, out_d + 3 * n, sizeof(double) * n, hipMemcpyDeviceToHost));
     return VA_OK;
 }
 

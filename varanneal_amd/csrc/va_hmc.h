@@ -26,6 +26,7 @@
 // workgroups in order, recomputed by every workgroup of the chain in commit -- no atomics, the same bits on every call.
 // The current action sits in A_cur[parity of the iteration][chain]: commit reads one parity and writes the other, so no
 // workgroup of a chain can see the word another one has already replaced.
+// Box bounds: va_hmc refuses a bounded handle; va_hmc_box.h runs these phases' arithmetic on an unconstrained z with x = T(z).
 #pragma once
 #include <math.h>
 #include <stdint.h>

@@ -69,4 +69,43 @@ inline int hmc_check_args(long n_var, long B, int n_iter, int n_leap, int thin, 
     return 0;
 }
 
+// ---------------------------------------------------------------- the box sampler's own checks (va_hmc_box.h)
+// kind[i] of every entry from its bounds (-/+HUGE_VAL: none): 0 free, 1 lower only, 2 upper only, 3 both.  Returns the
+// number of bounded entries (0: `why` says that nothing is bounded), or -1 with the reason in `why` (a lower bound that is
+// not below its upper bound, or a NaN).
+inline long hmc_box_kinds(long n_var, const double *lo, const double *hi, int32_t *kind, char *why, size_t nwhy)
+{
+    long nb = 0;
+    for (long i = 0; i < n_var; ++i) {
+        if (!(lo[i] < hi[i])) { snprintf(why, nwhy, "lower[%ld] = %g >= upper[%ld] = %g (or NaN)", i, lo[i], i, hi[i]); return -1; }
+        kind[i] = (lo[i] > -HUGE_VAL ? 1 : 0) + (hi[i] < HUGE_VAL ? 2 : 0);
+        if (kind[i]) ++nb;
+    }
+    if (nb == 0) snprintf(why, nwhy, "no bounds: every entry of lower / upper is infinite (va_hmc samples unbounded problems)");
+    return nb;
+}
+
+// a start X [B][ld] must lie strictly inside its box (T^-1 is infinite on a bound); 0, or 1 with the entry in `why`
+inline int hmc_box_check_start(long n_var, long B, long ld, const double *X, const double *lo, const double *hi, char *why, size_t nwhy)
+{
+    for (long b = 0; b < B; ++b)
+        for (long i = 0; i < n_var; ++i) {
+            const double v = X[b * ld + i];
+            if (!(v > lo[i] && v < hi[i]) || !std::isfinite(v)) {
+                snprintf(why, nwhy, "start XP[%ld][%ld] = %.17g is not strictly inside its box (%g, %g)", b, i, v, lo[i], hi[i]);
+                return 1;
+            }
+        }
+    return 0;
+}
+
+// a start given in z must be finite; 0, or 1 with the entry in `why`
+inline int hmc_box_check_z(long n_var, long B, long ld, const double *Z, char *why, size_t nwhy)
+{
+    for (long b = 0; b < B; ++b)
+        for (long i = 0; i < n_var; ++i)
+            if (!std::isfinite(Z[b * ld + i])) { snprintf(why, nwhy, "Z0[%ld][%ld] = %g is not finite", b, i, Z[b * ld + i]); return 1; }
+    return 0;
+}
+
 }  // namespace va

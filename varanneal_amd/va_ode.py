@@ -48,6 +48,46 @@ from ._ladder import LadderAnnealer
 _DISCS = ("euler", "trapezoid", "SimpsonHermite", "forwardmap")
 
 
+def hmc_box_inverse(X, lo, hi):
+    """z with T(z) = X for the map of csrc/va_hmc_box.h, entry by entry (lo, hi (n_var,), infinite: no bound); X strictly
+    inside.  One-sided: z = w - 1/w with w the distance to the bound; two-sided: z = u / sqrt((1 - u)(1 + u)),
+    u = 2 (x - lo)/(hi - lo) - 1."""
+    X = np.asarray(X, dtype=np.float64)
+    has_lo, has_hi = np.isfinite(lo), np.isfinite(hi)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        w = np.where(has_lo, X - lo, hi - X)
+        one = w - 1.0 / w
+        u = 2.0 * (X - lo) / (hi - lo) - 1.0
+        two = u / np.sqrt((1.0 - u) * (1.0 + u))
+    return np.where(has_lo & has_hi, two, np.where(has_lo | has_hi, one, X))
+
+
+def hmc_box_slope(Z, lo, hi):
+    """dx/dz of the same map at Z"""
+    Z = np.asarray(Z, dtype=np.float64)
+    has_lo, has_hi = np.isfinite(lo), np.isfinite(hi)
+    r = np.sqrt(Z * Z + 4.0)
+    w = np.where(Z >= 0.0, (Z + r) / 2.0, 2.0 / (r - Z))
+    q = np.sqrt(1.0 + Z * Z)
+    with np.errstate(invalid="ignore", over="ignore"):
+        two = (hi - lo) / (2.0 * (q * q * q))
+    one = np.where(has_lo, w / r, -(w / r))
+    return np.where(has_lo & has_hi, two, np.where(has_lo | has_hi, one, 1.0))
+
+
+def hmc_box_pull_in(X, lo, hi):
+    """(X with every entry on or outside a bound moved inside, how many per row): two-sided entries to 1e-6 (hi - lo) from
+    the bound they crossed, one-sided ones to 1e-6 max(1, |bound|)"""
+    X = np.array(X, dtype=np.float64)
+    has_lo, has_hi = np.isfinite(lo), np.isfinite(hi)
+    with np.errstate(invalid="ignore"):
+        d_lo = np.where(has_hi, 1e-6 * (hi - lo), 1e-6 * np.maximum(1.0, np.abs(lo)))
+        d_hi = np.where(has_lo, 1e-6 * (hi - lo), 1e-6 * np.maximum(1.0, np.abs(hi)))
+        low, high = has_lo & (X <= lo), has_hi & (X >= hi)
+        X = np.where(low, lo + d_lo, np.where(high, hi - d_hi, X))
+    return X, (low | high).sum(axis=1)
+
+
 def hmc_rescale_step(eps, accept_rate, target=0.8):
     """Warm-up rule of Annealer.sample: every chain's step size times 2^((rate - target) / (1 - target)) above the target
     acceptance rate and 2^((rate - target) / target) below it -- 1 at the target, monotone in the rate, never more than a
@@ -916,7 +956,17 @@ class Annealer(LadderAnnealer):
           mean, std (..., n_var)   accept_rate, n_divergent, step_size (...)   A, dH (..., n_samples * thin)
           x_last (..., n_samples, D), params (..., n_samples, NPest)  (keep=None)   or   kept (..., n_samples, len(keep))
           x (..., n_var) the final states;  seeds, rungs: the selection;  mass_note: per rung, None or why identity was used.
-        Box bounds: NotImplementedError."""
+        With `bounds` on the annealer the chains run through Problem.hmc_box (csrc/va_hmc_box.h): an unconstrained z with
+        x = T(z), every state inside its (closed) box and distributed as exp(-A) cut to it, whichever minimiser ran
+        (bounded_minimiser='scipy' too).  Everything returned speaks of x.  Far out in z an x rounds ONTO its bound: a
+        chain is continued through its z (as the rungs here are), not by passing such an x back as a start.  What differs:
+          starts     a minimiser entry on (or outside) a bound is pulled inside by 1e-6 (hi - lo), one-sided bounds by
+                     1e-6 max(1, |bound|); 'n_pulled_in' (...) counts the entries, per seed and rung (later rungs continue
+                     in z: 0)
+          mass       masses are those OF z: 'laplace' divides its variances by (dx/dz)^2 at the rung's start; an array is
+                     taken as given, in z
+          tails      T is algebraic, exp(-U) has polynomial tails in z: fine for bounds that guard, slow where the
+                     posterior piles up on a bound (watch accept_rate and the spread of kept values there)."""
         if self._pb is None or not getattr(self, "initalized", False):
             raise ValueError("sample() works after anneal() / anneal_init()")
         n_samples, n_leap, thin, warmup, warmup_block = int(n_samples), int(n_leap), int(thin), int(warmup), int(warmup_block)
@@ -937,13 +987,32 @@ class Annealer(LadderAnnealer):
             calls[0] += 1
             return (int(seed) + 0x9E3779B97F4A7C15 * calls[0]) & (2 ** 64 - 1)
         res, notes = [], []
+        boxed = self.bounds is not None
+        Z, pulled = None, np.zeros(B, np.int64)
+        if boxed:
+            lo = np.array([-np.inf if b[0] is None else b[0] for b in self.bounds], dtype=np.float64)
+            hi = np.array([np.inf if b[1] is None else b[1] for b in self.bounds], dtype=np.float64)
         for k in kb:
             rf = float(self._rf_scale[k])
             if XP is None:
                 src = self._mp[:, k]
                 XP = np.concatenate([src[:, :NX], src[:, NX:][:, self._estpos]], axis=1)
+                if boxed:
+                    XP, pulled = hmc_box_pull_in(XP, lo, hi)
             minv, note = self._hmc_mass(mass, k)
             notes.append(note)
+            if boxed and isinstance(mass, str) and minv is not None:
+                # laplace()'s variances are of x: var_z = var_x / (dx/dz)^2 at the rung's start (rows left at identity stay)
+                slope = hmc_box_slope(hmc_box_inverse(XP, lo, hi) if Z is None else Z, lo, hi)
+                with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+                    conv = minv / (slope * slope)
+                laplace_row = ~np.all(minv == 1.0, axis=1)
+                ok = np.all(np.isfinite(conv) & (conv > 0.0), axis=1)
+                minv = np.where((laplace_row & ok)[:, None], conv, np.where(laplace_row[:, None], 1.0, minv))
+                if np.any(laplace_row & ~ok):
+                    why = ("identity mass for seed(s) %s: the Laplace variance over (dx/dz)^2 is not finite at the start"
+                           % [int(b) for b in np.flatnonzero(laplace_row & ~ok)])
+                    notes[-1] = why if notes[-1] is None else notes[-1] + "; " + why
             if step_size is None:
                 eps = np.full(B, float(n_var) ** -0.25 * (1.0 if minv is not None else 0.01))
             else:
@@ -951,10 +1020,20 @@ class Annealer(LadderAnnealer):
             done = 0
             while done < warmup:
                 nb = min(warmup_block, warmup - done)
-                w = self._pb.hmc(XP, rf, nb, n_leap, eps, jitter=jitter, minv=minv, seed=call_seed())
+                if boxed:
+                    w = self._pb.hmc_box(XP, rf, nb, n_leap, eps, bounds=self.bounds, z0=Z, jitter=jitter, minv=minv, seed=call_seed())
+                    Z = w["z"]
+                else:
+                    w = self._pb.hmc(XP, rf, nb, n_leap, eps, jitter=jitter, minv=minv, seed=call_seed())
                 XP, done = w["x"], done + nb
                 eps = hmc_rescale_step(eps, w["accepted"].mean(axis=1))
-            r = self._pb.hmc(XP, rf, n_samples * thin, n_leap, eps, jitter=jitter, minv=minv, seed=call_seed(), thin=thin, keep_idx=keep_idx)
+            if boxed:
+                r = self._pb.hmc_box(XP, rf, n_samples * thin, n_leap, eps, bounds=self.bounds, z0=Z, jitter=jitter, minv=minv,
+                                     seed=call_seed(), thin=thin, keep_idx=keep_idx)
+                Z = r["z"]
+                r["n_pulled_in"], pulled = pulled, np.zeros(B, np.int64)
+            else:
+                r = self._pb.hmc(XP, rf, n_samples * thin, n_leap, eps, jitter=jitter, minv=minv, seed=call_seed(), thin=thin, keep_idx=keep_idx)
             XP = r["x"]
             r["step_size"] = eps
             res.append(r)
@@ -963,6 +1042,8 @@ class Annealer(LadderAnnealer):
         out = dict(mean=stack(lambda r: r["mean"]), std=stack(lambda r: np.sqrt(r["var"])), accept_rate=stack(lambda r: r["accepted"].mean(axis=1)),
                    A=stack(lambda r: r["A"]), dH=stack(lambda r: r["dH"]), n_divergent=stack(lambda r: r["n_divergent"]),
                    step_size=stack(lambda r: r["step_size"]), x=stack(lambda r: r["x"]), seeds=sb, rungs=kb, mass_note=notes)
+        if boxed:
+            out["n_pulled_in"] = stack(lambda r: r["n_pulled_in"])
         kept = stack(lambda r: r["kept"])
         if keep is None:
             out["x_last"], out["params"] = kept[..., :self.D], kept[..., self.D:]
