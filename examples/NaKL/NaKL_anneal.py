@@ -8,10 +8,14 @@ differentiates it and compiles f, J^T v and (df/dp)^T v for gfx950 on first use.
 tutorial's voltage recording is not shipped with the reference: a twin experiment is
 integrated here instead.
 
-    python examples/NaKL/NaKL_anneal.py [--nbeta 40] [--N 501] [--sample 200]
+    python examples/NaKL/NaKL_anneal.py [--nbeta 40] [--N 501] [--sample 200] [--shoot [--forecast 100]]
 
 --sample N draws N states per chain at the last rung inside the bounds (Annealer.sample through the box sampler,
 csrc/va_hmc_box.h) and prints every parameter as mean +- std beside its true value.
+--shoot refines the last rung to a model trajectory inside the same bounds, minimiser on the device
+(Annealer.shoot(device=True, box=True): L-BFGS-B in one launch, csrc/va_shoot_box.h), and prints p, cost, path_distance,
+how many entries ended on a bound, and the RMS error of a --forecast step voltage forecast from path[-1] against the twin's
+held-back truth beside the annealed path's.
 """
 import argparse
 import os
@@ -67,9 +71,14 @@ def main():
     ap.add_argument("--N", type=int, default=501)
     ap.add_argument("--out", default=".")
     ap.add_argument("--sample", type=int, default=0, help="posterior samples per chain at the last rung (0: none)")
+    ap.add_argument("--shoot", action="store_true", help="strong-constraint fit inside the bounds on the device (shoot(device=True, box=True))")
+    ap.add_argument("--forecast", type=int, default=100, help="with --shoot: model steps forecast past the data window")
     args = ap.parse_args()
     dt = 0.02
-    t, Iext, Y, truth = twin_data(args.N, dt)
+    n_fc = args.forecast if args.shoot else 0
+    t, Iext, Y, truth = twin_data(args.N + n_fc, dt)
+    I_future, V_future = Iext[args.N - 1:, None], truth[args.N - 1:, 0]          # from the last fitted time on
+    t, Iext, Y, truth = t[:args.N], Iext[:args.N], Y[:args.N], truth[:args.N]
 
     anneal1 = va_ode.Annealer()
     anneal1.set_model(nakl, 4)
@@ -100,6 +109,23 @@ def main():
         mean, std = np.asarray(r["mean"]).reshape(-1)[-18:], np.asarray(r["std"]).reshape(-1)[-18:]
         for i in range(18):
             print("  p[%2d] = %10.4f +- %-10.4f (true %8.3f, bounds [%g, %g])" % (i, mean[i], std[i], P_TRUE[i], PB[i][0], PB[i][1]))
+
+    if args.shoot:
+        sh = anneal1.shoot(beta=-1, device=True, box=True)
+        x0, par = sh["x0"].reshape(-1, 4)[0], sh["params"].reshape(-1, 18)[0]
+        z, lo, hi = np.append(x0, par), np.array([b[0] for b in XB + PB]), np.array([b[1] for b in XB + PB])
+        print("\nmodel trajectory fitted to the data window inside the bounds (Annealer.shoot(device=True, box=True)): status %d after "
+              "%d evaluations, %d iterations" % (sh["status"].ravel()[0], sh["nfev"].ravel()[0], sh["nit"].ravel()[0]))
+        print("p =", np.round(par, 4))
+        print("cost %.6g from %.6g   path_distance %.4g   entries on a bound: %d of %d"
+              % (sh["cost"].ravel()[0], sh["cost_start"].ravel()[0], sh["path_distance"].ravel()[0], int(np.sum((z == lo) | (z == hi))), z.size))
+        if n_fc > 0:
+            end = sh["path"].reshape(-1, args.N, 4)[0, -1]
+            fc = anneal1._pb.predict(end, par, n_fc, t0=float(t[-1]), stim=I_future)[0]
+            an = np.asarray(anneal1.predict(n_fc, beta=-1, stim=I_future)).reshape(-1, n_fc + 1, 4)[0]
+            rms = lambda v: float(np.sqrt(np.mean((v[1:, 0] - V_future[1:]) ** 2)))
+            print("voltage forecast over %d steps, RMS error against the twin: from path[-1] %.4g mV, from the annealed path %.4g mV"
+                  % (n_fc, rms(fc), rms(an)))
 
 
 if __name__ == "__main__":

@@ -330,6 +330,26 @@ int va_shoot(va_handle h, const double *x0, const double *p, const double *Y, co
              int64_t maxfun, int32_t maxls, double ftol, double gtol, double *x0_out, double *p_out, double *cost,
              double *cost_start, double *grad_max, int32_t *nit, int32_t *nfev, int32_t *status);
 
+/* va_shoot inside a box (csrc/va_shoot_box.h): the same misfit, minimised subject to lower <= [x0 | p_est] <= upper by
+ * L-BFGS-B, one lane per point running the published algorithm between evaluations (Byrd, Lu, Nocedal & Zhu 1995; Algorithm
+ * 778 in its 3.0 form, the one SciPy runs: generalised Cauchy point, subspace minimisation over the free variables with the
+ * projection step, dcsrch limited by the largest feasible step).  Arguments and outputs as va_shoot, and
+ *   lower, upper [n] (box_shared != 0: one table for all points) or [T*n], n = D + NPest: the D state columns, then the
+ *        estimated parameters in Pidx order; -inf / +inf: no bound
+ * The start is projected onto the box first: cost_start is the cost of the PROJECTED start.  grad_max [T] is the
+ * projected-gradient norm at the returned point (it takes the largest gradient entry's place in the gtol test).  Every
+ * returned entry satisfies lower <= x <= upper exactly; a finite, feasible iterate comes back in every case.  The same bits
+ * on every call, and whichever points share a launch.
+ * The handle's own bounds table is not looked at (as in va_hess_vec): the caller's box is the box, on bounded and unbounded
+ * handles alike.  va_shoot keeps refusing bounded handles.
+ * VA_EINVAL: what va_shoot rejects; lower / upper NULL; an entry with lower > upper or NaN (named in va_last_error).
+ * VA_EUNSUPPORTED: what va_shoot refuses, but for the handle's bounds. */
+int va_shoot_box(va_handle h, const double *x0, const double *p, const double *Y, const double *weights, int32_t y_shared, int32_t T,
+                 double t0, int32_t n_steps, int32_t substeps, int32_t every, const double *stim, int32_t m, int64_t maxiter,
+                 int64_t maxfun, int32_t maxls, double ftol, double gtol, const double *lower, const double *upper, int32_t box_shared,
+                 double *x0_out, double *p_out, double *cost, double *cost_start, double *grad_max, int32_t *nit, int32_t *nfev,
+                 int32_t *status);
+
 /* Lyapunov spectra of the handle's model (csrc/va_lyap.h): T trajectories from x0 with the parameters p, each with K <= D
  * tangents carried by the tangent-linear model of the RK4 integrator (va_predict's steps, stage times and stimulus; the
  * parameter tangent is zero) and re-orthonormalised together by a thin QR with positive diagonal after every qr_every model

@@ -213,6 +213,9 @@ def lib():
     L.va_shoot.argtypes = [h, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_dp, C.c_int32,
                            C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double] + [c_dp] * 5 + [c_ip] * 3
     L.va_shoot.restype = C.c_int
+    L.va_shoot_box.argtypes = [h, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_dp, C.c_int32,
+                               C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, c_dp, c_dp, C.c_int32] + [c_dp] * 5 + [c_ip] * 3
+    L.va_shoot_box.restype = C.c_int
     L.va_lyapunov.argtypes = [h, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_double] + [C.c_int32] * 4 + [c_dp] * 5 + [c_ip]
     L.va_lyapunov.restype = C.c_int
     L.va_enkf.argtypes = [h, c_dp, c_dp, c_ip, C.c_int32, c_dp, c_dp, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
@@ -266,7 +269,7 @@ def lib():
 
 EXPORTS = ["va_abi_version", "va_last_error", "va_device_count", "va_rhs_load_module", "va_act_load_module", "va_eval_plan", "va_eval_plan_reach", "va_problem_eval_kernel", "va_problem_eval_grid", "va_problem_tune", "va_problem_create",
            "va_problem_destroy", "va_problem_info", "va_action_grad", "va_minimize_lbfgs",
-           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_predict_adjoint", "va_shoot", "va_lyapunov", "va_enkf", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_box", "va_hmc_box_map", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
+           "va_anneal", "va_get_minpath", "va_predict", "va_predict_tangent", "va_predict_adjoint", "va_shoot", "va_shoot_box", "va_lyapunov", "va_enkf", "va_hess_vec", "va_blocktri_selinv", "va_laplace", "va_hmc", "va_hmc_box", "va_hmc_box_map", "va_hmc_noise", "va_eval_timed", "va_eval_timed_prepare", "va_problem_persistent", "va_debug_read_persist", "va_get_counters", "va_nnet_problem_create", "va_debug_read_partials",
            "va_read_eval_outputs", "va_lbfgs_timed", "va_eval_ls_timed", "va_comm_unique_id", "va_comm_create", "va_comm_destroy",
            "va_gather_results"]
 
@@ -661,6 +664,58 @@ class Problem(object):
         check(self._L.va_shoot(self._h, ptr(x0), ptr(p), ptr(Y), ptr(w), 1 if Y.ndim == 2 else 0, T, float(t0), n_steps, substeps, every,
                                ptr(st), int(m), int(maxiter), int(maxfun), int(maxls), float(ftol), float(gtol), ptr(r["x0"]), ptr(r["p"]),
                                ptr(r["cost"]), ptr(r["cost_start"]), ptr(r["grad_max"]), iptr(r["nit"]), iptr(r["nfev"]), iptr(r["status"])))
+        return r
+
+    def shoot_box(self, x0, p, n_steps, Y, weights, lower, upper, t0=0.0, substeps=1, every=1, stim=None, m=10, maxiter=15000,
+                  maxfun=15000, maxls=20, ftol=1e-15, gtol=1e-9):
+        """shoot() inside a box (va_shoot_box; csrc/va_shoot_box.h): the same misfit over x0 and the estimated parameters,
+        subject to lower <= [x0 | p_est] <= upper, by L-BFGS-B (the published algorithm SciPy runs: generalised Cauchy point,
+        subspace minimisation with the 3.0 projection step, dcsrch), every point's whole minimisation in one launch.
+        lower, upper: (n,) for all points or (T, n), n = D + NPest: the D state columns, then the estimated parameters in
+        Pidx order; None, -inf / +inf: no bound.  The start is projected onto the box; cost_start is the projected start's
+        cost.  Returns shoot's dict; grad_max is the projected-gradient norm at the returned point, and every returned
+        entry satisfies lower <= x <= upper exactly.  The handle's own bounds are not looked at: the caller's box is the box."""
+        if not isinstance(self.desc, ProblemDesc):
+            raise NotImplementedError("shoot_box: a network handle has no differential equation to integrate")
+        D, NP, Ld, nv = self.desc.D, self.desc.NP, self.desc.L, self.desc.D + self.desc.NPest
+        x0 = _f64(x0).reshape(-1, D)
+        T = x0.shape[0]
+        p = _f64(p).reshape(-1, NP) if NP else np.zeros((T, 0))
+        if p.shape[0] == 1 and T > 1:
+            p = np.ascontiguousarray(np.broadcast_to(p, (T, NP)))
+        if p.shape[0] != T:
+            raise ValueError("shoot_box: %d states but %d parameter vectors" % (T, p.shape[0]))
+        n_steps, substeps, every = int(n_steps), int(substeps), int(every)
+        n_out = n_steps // every + 1 if every >= 1 and n_steps >= 1 else 1
+        st = None
+        if stim is not None:
+            st = _f64(stim).reshape(max(n_steps, 0) + 1, -1)
+            if st.shape[1] != self.desc.n_stim and self.desc.n_stim:
+                raise ValueError("shoot_box: the stimulus must have %d rows of %d column(s)" % (n_steps + 1, self.desc.n_stim))
+        Y = _f64(Y)
+        if Y.shape not in ((n_out, Ld), (T, n_out, Ld)):
+            raise ValueError("shoot_box: Y must have shape (n_out = %d, L = %d) or (%d, %d, %d), got %s" % (n_out, Ld, T, n_out, Ld, Y.shape))
+        w = _f64(weights)
+        if w.shape != (Ld,):
+            raise ValueError("shoot_box: weights must have shape (L = %d,), got %s" % (Ld, w.shape))
+
+        def side(b, none, name):
+            b = np.asarray(b, dtype=object)
+            if b.shape not in ((nv,), (T, nv)):
+                raise ValueError("shoot_box: %s must have shape (n = %d,) or (%d, %d), got %s" % (name, nv, T, nv, b.shape))
+            return np.ascontiguousarray(np.where(np.equal(b, None), none, b).astype(np.float64))
+        lo, hi = side(lower, -np.inf, "lower"), side(upper, np.inf, "upper")
+        if lo.shape != hi.shape:
+            raise ValueError("shoot_box: lower %s and upper %s must have the same shape" % (lo.shape, hi.shape))
+        shared = lo.ndim == 1
+        r = dict(x0=np.empty((T, D)), p=np.empty((T, NP)), cost=np.empty(T), cost_start=np.empty(T), grad_max=np.empty(T),
+                 nit=np.empty(T, dtype=np.int32), nfev=np.empty(T, dtype=np.int32), status=np.empty(T, dtype=np.int32))
+        ptr = lambda a: a.ctypes.data_as(c_dp) if a is not None else None
+        iptr = lambda a: a.ctypes.data_as(c_ip)
+        check(self._L.va_shoot_box(self._h, ptr(x0), ptr(p), ptr(Y), ptr(w), 1 if Y.ndim == 2 else 0, T, float(t0), n_steps, substeps,
+                                   every, ptr(st), int(m), int(maxiter), int(maxfun), int(maxls), float(ftol), float(gtol), ptr(lo), ptr(hi),
+                                   1 if shared else 0, ptr(r["x0"]), ptr(r["p"]), ptr(r["cost"]), ptr(r["cost_start"]), ptr(r["grad_max"]),
+                                   iptr(r["nit"]), iptr(r["nfev"]), iptr(r["status"])))
         return r
 
     def lyapunov(self, x0, p, K, n_steps, t0=0.0, substeps=1, qr_every=1, n_skip=0, Q0=None, coupling=None, stim=None, trace=False):

@@ -996,7 +996,7 @@ BUILD_TAG = "sched=iterative-maxocc"      # part of every module's cache key: a 
 def _core_fingerprint():
     h = hashlib.sha1(BUILD_TAG.encode())
     for fn in ("va_core.h", "va_device.h", "va_eval_flat.h", "va_eval3.h", "va_eval4.h", "va_epilogue.h", "va_tile2.h", "va_tile3.h",
-               "va_tile4.h", "va_tile5.h", "va_eval5.h", "va_persist.h", "va_persist_geo.h", "va_measure.h", "va_predict.h", "va_predict_geo.h", "va_predict_tlm.h", "va_predict_tlm_geo.h", "va_predict_adj.h", "va_predict_adj_geo.h", "va_shoot.h", "va_shoot_geo.h",
+               "va_tile4.h", "va_tile5.h", "va_eval5.h", "va_persist.h", "va_persist_geo.h", "va_measure.h", "va_predict.h", "va_predict_geo.h", "va_predict_tlm.h", "va_predict_tlm_geo.h", "va_predict_adj.h", "va_predict_adj_geo.h", "va_shoot.h", "va_shoot_box.h", "va_shoot_geo.h",
                "va_lyap.h", "va_lyap_geo.h", "va_enkf.h", "va_enkf_geo.h",
                "va_hvp.h", "va_hvp_geo.h",
                "va_user_rhs.hip"):

@@ -41,6 +41,7 @@
 #include "va_predict_tlm.h"
 #include "va_predict_adj.h"
 #include "va_shoot.h"
+#include "va_shoot_box.h"
 #include "va_lyap.h"
 #include "va_enkf.h"
 #include "va_hvp.h"
@@ -993,7 +994,8 @@ int va_rhs_load_module(const char *path, int32_t *rhs_id)
         const int hb = hv(&u.hvp, (int)sizeof(HvpTable));
         if (hb != (int)sizeof(HvpTable) || u.hvp.hvp_bytes != (int)sizeof(HvpArgs) || u.hvp.tlm_bytes != (int)sizeof(PredictTlmArgs)
             || u.hvp.lyap_bytes != (int)sizeof(LyapArgs) || u.hvp.adj_bytes != (int)sizeof(PredictAdjArgs)
-            || u.hvp.shoot_bytes != (int)sizeof(ShootArgs) || u.hvp.enkf_bytes != (int)sizeof(EnkfArgs)) {
+            || u.hvp.shoot_bytes != (int)sizeof(ShootArgs) || u.hvp.enkf_bytes != (int)sizeof(EnkfArgs)
+            || u.hvp.shoot_box_bytes != (int)sizeof(ShootBoxArgs)) {
             dlclose(u.dl);
             return fail(VA_EINVAL, "%s was built against different headers (HvpTable %d vs %zu bytes): rebuild it", path, hb, sizeof(HvpTable));
         }
@@ -1514,6 +1516,119 @@ int va_shoot(va_handle h, const double *x0, const double *p, const double *Y, co
         HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
         for (long k = 0; k < n; ++k) {
             const ShootState &s = states[(size_t)k];
+            cost[t1 + k] = s.f; cost_start[t1 + k] = s.f_start; grad_max[t1 + k] = s.gmax;
+            nit[t1 + k] = s.iter; nfev[t1 + k] = (int32_t)s.nfev; status[t1 + k] = s.status;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return VA_OK;
+}
+
+// Strong-constraint shooting inside a box (va_shoot_box.h): va_shoot's launch with L-BFGS-B as the step.  The caller's box is
+// the box: the handle's own `bounds` table is not looked at (as va_hess_vec ignores it), so bounded and unbounded handles
+// both run.  Buffers and chunking as va_shoot, with the larger per-point workspace and, when every point has its own box,
+// 2 n doubles more per point.
+int va_shoot_box(va_handle h, const double *x0, const double *p, const double *Y, const double *weights, int32_t y_shared, int32_t T,
+                 double t0, int32_t n_steps, int32_t substeps, int32_t every, const double *stim, int32_t m, int64_t maxiter,
+                 int64_t maxfun, int32_t maxls, double ftol, double gtol, const double *lower, const double *upper, int32_t box_shared,
+                 double *x0_out, double *p_out, double *cost, double *cost_start, double *grad_max, int32_t *nit, int32_t *nfev,
+                 int32_t *status)
+{
+    if (!h) return fail(VA_EINVAL, "null handle");
+    if (!x0 || !p || !Y || !weights) return fail(VA_EINVAL, "va_shoot_box: x0 / p / Y / weights must not be NULL");
+    if (!lower || !upper) return fail(VA_EINVAL, "va_shoot_box: lower / upper must not be NULL (-inf / +inf entries: no bound)");
+    if (!x0_out || !p_out || !cost || !cost_start || !grad_max || !nit || !nfev || !status) return fail(VA_EINVAL, "va_shoot_box: the outputs must not be NULL");
+    if (T < 1 || n_steps < 1 || substeps < 1 || every < 1)
+        return fail(VA_EINVAL, "T, n_steps, substeps and every must be at least 1 (T=%d n_steps=%d substeps=%d every=%d)", T, n_steps, substeps, every);
+    char why[192];
+    if (!shoot_check_args(m, maxiter, maxfun, maxls, why, sizeof why)) return fail(VA_EINVAL, "va_shoot_box: %s", why);
+    if (h->is_nnet) return fail(VA_EUNSUPPORTED, "a network handle has no differential equation to integrate");
+    const Dims &dm = h->dv.dm;
+    const int nstim = h->dv.pp.nstim;
+    if (nstim > 0 && !stim) return fail(VA_EINVAL, "the model takes a stimulus of %d column(s): pass its %d rows from t0 on", nstim, n_steps + 1);
+    if (nstim == 0 && stim) return fail(VA_EINVAL, "the model takes no stimulus, but one was passed");
+    if (dm.lin) return fail(VA_EUNSUPPORTED, "va_shoot_box: the module's dense linear part was split off (LINEAR): build it with linear=False");
+    if (dm.D > SHOOT_MAX_D)
+        return fail(VA_EUNSUPPORTED, "va_shoot_box: D=%d: the shooting kernel carries states of at most %d columns; minimise on the host around va_predict_adjoint",
+                    dm.D, SHOOT_MAX_D);
+    if (!h->rt.predict || !h->rt_hvp.predict_adj || !h->rt_hvp.shoot_box)
+        return fail(VA_EUNSUPPORTED, "va_shoot_box: the model has no flat form f(x, i, p) to differentiate (more than %d parameters: "
+                                     "its module carries the column-parameter form only)", RHS_BIG_NP);
+    if ((int64_t)n_steps * substeps > 2000000000LL) return fail(VA_EUNSUPPORTED, "n_steps x substeps does not fit 32-bit indexing");
+    const int nvar = dm.D + dm.NPest;
+    if (!shoot_box_check_bounds(lower, upper, box_shared ? 1 : (long)T, nvar, why, sizeof why)) return fail(VA_EINVAL, "va_shoot_box: %s", why);
+    ShootBoxArgs ba;
+    ShootArgs &sa = ba.sh;
+    PredictAdjArgs &a = sa.adj;
+    a.T = T; a.D = dm.D; a.NP = dm.NPt; a.NPest = dm.NPest; a.ncot = 1; a.L = dm.L; a.nstim = nstim; a.n_steps = n_steps;
+    a.substeps = substeps; a.every = every; a.n_out = n_steps / every + 1; a.t0 = t0; a.dt = dm.dt; a.Pidx = h->dv.pp.Pidx;
+    a.G = nullptr; a.out = nullptr;
+    sa.m = m; sa.maxls = maxls; sa.maxiter = maxiter; sa.maxfun = maxfun; sa.ftol = ftol; sa.gtol = gtol; sa.st = nullptr;
+    ba.box_shared = box_shared ? 1 : 0;
+    const long long Q = (long long)n_steps * substeps;
+    const size_t yrow = (size_t)a.n_out * a.L, brow = 2 * (size_t)nvar;
+    ShootGeo geo;
+    if (!plan_shoot_box(a.D, T, a.NP, a.NPest, nstim, m, geo)) return fail(VA_EUNSUPPORTED, "va_shoot_box: D=%d: %s", a.D, geo.why);
+    const size_t per = shoot_box_traj_doubles(a.D, a.NP, a.NPest, Q, m, y_shared ? 0 : yrow, box_shared ? 0 : brow);
+    const size_t spare = (size_t)geo.adj.RW * (size_t)Q * a.D + (size_t)(n_steps + 1) * nstim + yrow + brow + 2 * (size_t)a.L + 8;
+    const long C = predict_adj_chunk_trajs(per, spare, T);
+    if (C < 1)
+        return fail(VA_EUNSUPPORTED, "va_shoot_box: one point with %d output row(s), %lld checkpoints and %d history pair(s) takes %.1f MiB of "
+                                     "device workspace, the limit is %zu MiB: fewer steps, or a larger `every`", a.n_out, Q, m,
+                    (double)(per + spare) * 8.0 / 1048576.0, PREDICT_ADJ_WORKSPACE_BYTES >> 20);
+    if (!plan_shoot_box(a.D, C, a.NP, a.NPest, nstim, m, geo)) return fail(VA_EUNSUPPORTED, "va_shoot_box: D=%d: %s", a.D, geo.why);
+    HIPCHK(hipSetDevice(h->device));
+    // one allocation: [stim | w | Lidx | x0 | p | Y | lower | upper | gx0 | gp | cost | states | minimiser workspace | checkpoints]
+    const size_t sd = shoot_box_state_doubles();
+    const size_t ns = (size_t)(n_steps + 1) * nstim, nwt = a.L, nli = ((size_t)a.L + 1) / 2, nx = (size_t)C * a.D, np = (size_t)C * a.NP,
+                 ny = y_shared ? yrow : (size_t)C * yrow, nbx = box_shared ? (size_t)nvar : (size_t)C * nvar, ngp = (size_t)C * a.NPest,
+                 nc = (size_t)C, nst = (size_t)C * sd, nwk = (size_t)C * geo.point_doubles, nck = predict_adj_ckpt_doubles(geo.adj, a.D, Q);
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (ns + nwt + nli + nx + np + ny + 2 * nbx + nx + ngp + nc + nst + nwk + nck + 1)));
+    struct Free { double *q; ~Free() { (void)hipFree(q); } } guard{buf};
+    double *st_d = buf, *w_d = st_d + ns, *li_d = w_d + nwt, *x0_d = li_d + nli, *p_d = x0_d + nx, *y_d = p_d + np, *lo_d = y_d + ny,
+           *hi_d = lo_d + nbx, *gx_d = hi_d + nbx, *gp_d = gx_d + nx, *c_d = gp_d + ngp, *s_d = c_d + nc, *wk_d = s_d + nst, *ck_d = wk_d + nwk;
+    if (ns) HIPCHK(hipMemcpyAsync(st_d, stim, sizeof(double) * ns, hipMemcpyHostToDevice, h->stream));
+    if (a.L) {
+        HIPCHK(hipMemcpyAsync(w_d, weights, sizeof(double) * a.L, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(li_d, h->lidx_user.data(), sizeof(int) * a.L, hipMemcpyHostToDevice, h->stream));
+        if (y_shared) HIPCHK(hipMemcpyAsync(y_d, Y, sizeof(double) * yrow, hipMemcpyHostToDevice, h->stream));
+    }
+    if (box_shared) {
+        HIPCHK(hipMemcpyAsync(lo_d, lower, sizeof(double) * nvar, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(hi_d, upper, sizeof(double) * nvar, hipMemcpyHostToDevice, h->stream));
+    }
+    std::vector<ShootBoxState> states((size_t)C);
+    for (long t1 = 0; t1 < T; t1 += C) {
+        const long n = T - t1 < C ? T - t1 : C;
+        HIPCHK(hipMemcpyAsync(x0_d, x0 + (size_t)t1 * a.D, sizeof(double) * n * a.D, hipMemcpyHostToDevice, h->stream));
+        if (a.NP) HIPCHK(hipMemcpyAsync(p_d, p + (size_t)t1 * a.NP, sizeof(double) * n * a.NP, hipMemcpyHostToDevice, h->stream));
+        if (!y_shared && yrow) HIPCHK(hipMemcpyAsync(y_d, Y + (size_t)t1 * yrow, sizeof(double) * n * yrow, hipMemcpyHostToDevice, h->stream));
+        if (!box_shared) {
+            HIPCHK(hipMemcpyAsync(lo_d, lower + (size_t)t1 * nvar, sizeof(double) * n * nvar, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(hi_d, upper + (size_t)t1 * nvar, sizeof(double) * n * nvar, hipMemcpyHostToDevice, h->stream));
+        }
+        a.T = (int)n;
+        if (!plan_shoot_box(a.D, n, a.NP, a.NPest, nstim, m, geo) || predict_adj_ckpt_doubles(geo.adj, a.D, Q) > nck) {      // (the last chunk: the same plan on fewer workgroups)
+            (void)hipStreamSynchronize(h->stream);
+            return fail(VA_EUNSUPPORTED, "va_shoot_box: D=%d: %s", a.D, geo.why);
+        }
+        a.geo = geo.adj;
+        a.x0 = x0_d; a.p = p_d; a.Y = y_d; a.w = w_d; a.Lidx = (const int *)li_d; a.y_stride = y_shared ? 0 : yrow;
+        a.stim = ns ? st_d : nullptr; a.gx0 = gx_d; a.gp = gp_d; a.cost = c_d; a.ckpt = ck_d;
+        sa.x = x0_d; sa.p = p_d; sa.work = wk_d; sa.point_doubles = geo.point_doubles;
+        ba.st = (ShootBoxState *)s_d; ba.lower = lo_d; ba.upper = hi_d;
+        const hipError_t e = h->rt_hvp.shoot_box(ba, h->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);       // (the uploads read the caller's arrays)
+            return fail(VA_EHIP, "k_shoot_box launch: %s", hipGetErrorString(e));
+        }
+        HIPCHK(hipMemcpyAsync(x0_out + (size_t)t1 * a.D, x0_d, sizeof(double) * n * a.D, hipMemcpyDeviceToHost, h->stream));
+        if (a.NP) HIPCHK(hipMemcpyAsync(p_out + (size_t)t1 * a.NP, p_d, sizeof(double) * n * a.NP, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(states.data(), s_d, sizeof(ShootBoxState) * n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));      // (the next chunk reuses the buffers; pageable destinations)
+        for (long k = 0; k < n; ++k) {
+            const ShootBoxState &s = states[(size_t)k];
             cost[t1 + k] = s.f; cost_start[t1 + k] = s.f_start; grad_max[t1 + k] = s.gmax;
             nit[t1 + k] = s.iter; nfev[t1 + k] = (int32_t)s.nfev; status[t1 + k] = s.status;
         }

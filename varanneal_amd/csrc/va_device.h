@@ -156,17 +156,20 @@ struct LyapArgs;
 struct PredictAdjArgs;
 struct ShootArgs;
 struct EnkfArgs;
+struct ShootBoxArgs;
 struct HvpTable {
     int bytes, hvp_bytes, tlm_bytes, lyap_bytes;      // sizeof(HvpTable), sizeof(HvpArgs), sizeof(PredictTlmArgs), sizeof(LyapArgs)
     int adj_bytes;                                    // sizeof(PredictAdjArgs)
     int shoot_bytes;                                  // sizeof(ShootArgs)
     int enkf_bytes;                                   // sizeof(EnkfArgs)
+    int shoot_box_bytes;                              // sizeof(ShootBoxArgs)
     hipError_t (*hvp)(const HvpArgs &, size_t lds_bytes, hipStream_t);      // or NULL
     hipError_t (*predict_tlm)(const PredictTlmArgs &, hipStream_t);         // or NULL
     hipError_t (*lyap)(const LyapArgs &, hipStream_t);                      // or NULL
     hipError_t (*predict_adj)(const PredictAdjArgs &, hipStream_t);         // the adjoint predictor (va_predict_adj.h), or NULL
     hipError_t (*shoot)(const ShootArgs &, hipStream_t);                    // the shooting kernel (va_shoot.h), or NULL
     hipError_t (*enkf)(const EnkfArgs &, hipStream_t);                      // the ensemble Kalman filter (va_enkf.h), or NULL
+    hipError_t (*shoot_box)(const ShootBoxArgs &, hipStream_t);             // the boxed shooting kernel (va_shoot_box.h), or NULL
 };
 void builtin_hvp_table(HvpTable &t);
 

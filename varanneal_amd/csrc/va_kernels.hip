@@ -29,6 +29,7 @@
 #include "va_predict_tlm.h"
 #include "va_predict_adj.h"
 #include "va_shoot.h"
+#include "va_shoot_box.h"
 #include "va_lyap.h"
 #include "va_enkf.h"
 #include "va_hvp.h"
@@ -96,13 +97,13 @@ void builtin_rhs_table(RhsTable &t)
                  eval_builtin, nullptr, seed_op<RhsL96>, launch_predict<RhsL96, 0>};
 }
 // Hessian-vector products (va_hvp.h), the tangent-linear predictor (va_predict_tlm.h), Lyapunov spectra (va_lyap.h), the
-// adjoint predictor (va_predict_adj.h), the shooting kernel (va_shoot.h) and the ensemble Kalman filter (va_enkf.h)
+// adjoint predictor (va_predict_adj.h), the shooting kernels (va_shoot.h, va_shoot_box.h) and the ensemble Kalman filter (va_enkf.h)
 void builtin_hvp_table(HvpTable &t)
 {
     t = HvpTable{(int)sizeof(HvpTable), (int)sizeof(HvpArgs), (int)sizeof(PredictTlmArgs), (int)sizeof(LyapArgs),
-                 (int)sizeof(PredictAdjArgs), (int)sizeof(ShootArgs), (int)sizeof(EnkfArgs), launch_hvp<RhsL96>,
+                 (int)sizeof(PredictAdjArgs), (int)sizeof(ShootArgs), (int)sizeof(EnkfArgs), (int)sizeof(ShootBoxArgs), launch_hvp<RhsL96>,
                  launch_predict_tlm<RhsL96, 0>, launch_lyap<RhsL96, 0>, launch_predict_adj<RhsL96, 0>, launch_shoot<RhsL96, 0>,
-                 launch_enkf<RhsL96, 0>};
+                 launch_enkf<RhsL96, 0>, launch_shoot_box<RhsL96, 0>};
 }
 
 // ------------------------------------------------------------------ K2: tails as kernels of their own

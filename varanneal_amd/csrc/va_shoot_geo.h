@@ -89,4 +89,62 @@ inline size_t shoot_traj_doubles(int D, int NP, int NPest, long long Q, int m, s
     return (size_t)D + NP + y_doubles + (size_t)D + NPest + 1 + (size_t)Q * D + shoot_state_doubles() + shoot_point_doubles(D + NPest, m);
 }
 
+// ---------------------------------------------------------------- the boxed shoot (k_shoot_box, va_shoot_box.h)
+// The same workgroups, LDS and limits; what grows is the minimiser: one lane per point runs L-BFGS-B.  Its state is a struct
+// of its own (ShootState stays as it is), and its per-point workspace in global memory holds, in doubles,
+//   xk, gk, d, z, r, t, xp [n each]    the iterate, its gradient, the direction, the Cauchy / subspace point, the reduced
+//                                      gradient, the breakpoints, the point saved for subsm's backtrack;  n = D + NPest
+//   S [m][n], Y [m][n]                 the pairs, a ring of m columns
+//   sy, ss, wt [m m each]              S'Y, S'S, the factor of T = theta S'S + L D^-1 L'
+//   wn, wn1 [4 m m each]               the factored reduced middle matrix and its inner-product blocks, kept incrementally
+//   wa [8 m]                           cauchy's p, c, wbp, v
+// and behind them iwhere, index, iorder [n ints each], two ints to a double:
+//   shoot_box_point_doubles(n, m) = 7 n + 2 m n + 11 m m + 8 m + (3 n + 1) / 2
+// 14.6 KiB at D = 20, one parameter, m = 10; 218 KiB at D = 512, m = 10.
+struct ShootBoxState {
+    int phase, status;       // as ShootState
+    int iter, col, head;     // iterations; pairs stored; the oldest pair's column, 1-based (the published code's ring)
+    int itail, iupdat, updatd;     // the newest pair's column; pairs accepted since the memory was emptied; the last iteration stored one
+    int nls, nfree, nenter, ileave;     // trials of the search in progress; free variables at the Cauchy point; entered / left (freev)
+    int cnstnd, boxed, wnsync, pad0;    // any bound; every entry two-sided; wn1 holds every pair and the last free set
+    long long nfev;
+    double f, f_start, gmax; // cost at the iterate; cost of the projected start; projected-gradient norm sbgnrm at the iterate
+    double stp, stpmx, gdold, theta, dtd;
+    LsState ls;
+};
+
+inline size_t shoot_box_point_doubles(int n, int m)
+{
+    return 7 * (size_t)n + 2 * (size_t)m * n + 11 * (size_t)m * m + 8 * (size_t)m + (3 * (size_t)n + 1) / 2;
+}
+
+// plan_shoot's geometry with the larger workspace
+inline bool plan_shoot_box(int D, long T, int NP, int NPest, int nstim, int m, ShootGeo &g)
+{
+    if (!plan_shoot(D, T, NP, NPest, nstim, m, g)) return false;
+    g.point_doubles = shoot_box_point_doubles(g.n, m);
+    return true;
+}
+
+// the box: `count` tables of n entries (1 when shared); -inf / +inf: no bound.  false with the first bad entry named
+inline bool shoot_box_check_bounds(const double *lower, const double *upper, long count, int n, char *why, size_t len)
+{
+    for (long t = 0; t < count; ++t)
+        for (int i = 0; i < n; ++i) {
+            const double lo = lower[(size_t)t * n + i], hi = upper[(size_t)t * n + i];
+            if (lo != lo || hi != hi) { snprintf(why, len, "bounds: entry %d of table %ld is NaN", i, t); return false; }
+            if (lo > hi) { snprintf(why, len, "bounds: entry %d of table %ld has lower %.17g > upper %.17g", i, t, lo, hi); return false; }
+        }
+    return true;
+}
+
+// va_shoot_box's device buffers per point, as shoot_traj_doubles: the larger state and workspace, and the point's own box
+// (box_doubles = 2 n when every point has one, 0 when all share one table)
+inline size_t shoot_box_state_doubles() { return (sizeof(ShootBoxState) + sizeof(double) - 1) / sizeof(double); }
+inline size_t shoot_box_traj_doubles(int D, int NP, int NPest, long long Q, int m, size_t y_doubles, size_t box_doubles)
+{
+    return (size_t)D + NP + y_doubles + box_doubles + (size_t)D + NPest + 1 + (size_t)Q * D + shoot_box_state_doubles()
+           + shoot_box_point_doubles(D + NPest, m);
+}
+
 }  // namespace va

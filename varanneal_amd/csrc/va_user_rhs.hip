@@ -20,6 +20,7 @@
 #include "va_predict_tlm.h"
 #include "va_predict_adj.h"
 #include "va_shoot.h"
+#include "va_shoot_box.h"
 #include "va_lyap.h"
 #include "va_enkf.h"
 #include "va_hvp.h"
@@ -78,13 +79,13 @@ template <class R> void fill_table(va::RhsTable &t)
 template <class R> void fill_hvp_table(va::HvpTable &t)
 {
     t = va::HvpTable{(int)sizeof(va::HvpTable), (int)sizeof(va::HvpArgs), (int)sizeof(va::PredictTlmArgs), (int)sizeof(va::LyapArgs),
-                     (int)sizeof(va::PredictAdjArgs), (int)sizeof(va::ShootArgs), (int)sizeof(va::EnkfArgs), nullptr, nullptr, nullptr,
-                     nullptr, nullptr, nullptr};
+                     (int)sizeof(va::PredictAdjArgs), (int)sizeof(va::ShootArgs), (int)sizeof(va::EnkfArgs), (int)sizeof(va::ShootBoxArgs), nullptr, nullptr,
+                     nullptr, nullptr, nullptr, nullptr, nullptr};
     if constexpr (va::rhs_flat<R>::value) t.enkf = va::launch_enkf<R, R::D>;
     if constexpr (va::rhs_flat<R>::value && !va::rhs_linear<R>::value) {
         t.hvp = va::launch_hvp<R>; t.predict_tlm = va::launch_predict_tlm<R, R::D>;
         t.predict_adj = va::launch_predict_adj<R, R::D>;
-        if constexpr (R::D <= va::SHOOT_MAX_D) t.shoot = va::launch_shoot<R, R::D>;
+        if constexpr (R::D <= va::SHOOT_MAX_D) { t.shoot = va::launch_shoot<R, R::D>; t.shoot_box = va::launch_shoot_box<R, R::D>; }
         if constexpr (R::D <= va::LYAP_MAX_D) t.lyap = va::launch_lyap<R, R::D>;
     }
 }

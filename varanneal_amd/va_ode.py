@@ -509,7 +509,7 @@ class Annealer(LadderAnnealer):
 
     _SHOOT_DEVICE_OPTS = dict(ftol="ftol", gtol="gtol", maxiter="maxiter", maxfun="maxfun", maxcor="m", maxls="maxls")
 
-    def shoot(self, beta=-1, seeds=None, substeps=1, opt_args=None, device=False):
+    def shoot(self, beta=-1, seeds=None, substeps=1, opt_args=None, device=False, box=False):
         """The RF -> infinity limit, done exactly: strong-constraint 4D-Var refinement of the selected (seed, rung)s.  A
         stored minimiser is a path, not a model orbit; this fits an actual model trajectory x(t; x(t_0), p) to the data
         window.  From the first row of the stored minimiser and that rung's parameters, SciPy's L-BFGS-B (host, one point at a
@@ -526,10 +526,17 @@ class Annealer(LadderAnnealer):
         (csrc/va_shoot.h: every point's L-BFGS from the first evaluation to the last inside one launch), then one predict()
         call for path.  The same keys, shapes and meanings, plus nit (iterations); nfev counts the kernel's evaluations;
         status 1 budget, 2 abnormal line search, 3 non-finite cost at the start.  opt_args: ftol, gtol, maxiter, maxfun,
-        maxcor, maxls (any other key: ValueError).  Annealer bounds: NotImplementedError (no projected step on the device);
-        D <= 512."""
+        maxcor, maxls (any other key: ValueError).  Annealer bounds: NotImplementedError unless box=True; D <= 512.
+        device=True, box=True: the device minimiser is L-BFGS-B (csrc/va_shoot_box.h, Problem.shoot_box): the annealer's
+        bounds on x(t_0) and on the estimated parameters -- self.bounds[:D] + self.bounds[NX:NX + NPest], what the host route
+        hands SciPy -- are one box for all selected points, in ONE shoot_box call, then one predict() call.  The same keys as
+        device=True; the start is projected onto the box (cost_start is the projected start's cost), grad_norm is the
+        projected-gradient norm, every returned entry lies inside its bounds exactly.  An annealer without bounds runs
+        with an all-infinite box.  box=True without device=True: ValueError."""
+        if box and not device:
+            raise ValueError("shoot(box=True) is the device route's L-BFGS-B: pass device=True (device=False already hands the bounds to SciPy)")
         if device:
-            return self._shoot_device(beta, seeds, substeps, opt_args)
+            return self._shoot_device(beta, seeds, substeps, opt_args, box)
         from scipy.optimize import minimize
         if self._pb is None or not getattr(self, "initalized", False):
             raise ValueError("shoot() works after anneal() / anneal_init()")
@@ -569,14 +576,14 @@ class Annealer(LadderAnnealer):
             out[k] = v.reshape(lead + v.shape[1:])
         return out
 
-    def _shoot_device(self, beta, seeds, substeps, opt_args):
+    def _shoot_device(self, beta, seeds, substeps, opt_args, box=False):
         if self._pb is None or not getattr(self, "initalized", False):
             raise ValueError("shoot() works after anneal() / anneal_init()")
         if self._tdp:
             raise NotImplementedError("shoot: time-dependent parameters have no single model trajectory to fit")
-        if self.bounds is not None:
-            raise NotImplementedError("shoot(device=True): bounds are not carried (the device minimiser takes no projected step); "
-                                      "use device=False")
+        if self.bounds is not None and not box:
+            raise NotImplementedError("shoot(device=True): bounds are not carried by the unbounded device minimiser (it takes no "
+                                      "projected step); pass box=True for L-BFGS-B on the device, or use device=False")
         kw = {}
         for k, v in dict(self.SHOOT_OPT_ARGS, **(opt_args or {})).items():
             if k not in self._SHOOT_DEVICE_OPTS:
@@ -588,8 +595,16 @@ class Annealer(LadderAnnealer):
         stim = None if self.stim is None else np.asarray(self.stim, dtype=np.float64)
         t0 = float(self.t_model[0])
         rows = self._mp[sb][:, kb].reshape(len(sb) * len(kb), -1)
-        r = self._pb.shoot(rows[:, :D], rows[:, NX:NX + NP], N - 1, np.ascontiguousarray(self.Y, dtype=np.float64), w, t0=t0,
-                           substeps=substeps, every=self.merr_nskip, stim=stim, **kw)
+        if box:
+            bounds = [(None, None)] * (D + self.NPest)
+            if self.bounds is not None:
+                bounds = list(self.bounds[:D]) + list(self.bounds[NX:NX + self.NPest])
+            r = self._pb.shoot_box(rows[:, :D], rows[:, NX:NX + NP], N - 1, np.ascontiguousarray(self.Y, dtype=np.float64), w,
+                                   [b[0] for b in bounds], [b[1] for b in bounds], t0=t0, substeps=substeps, every=self.merr_nskip,
+                                   stim=stim, **kw)
+        else:
+            r = self._pb.shoot(rows[:, :D], rows[:, NX:NX + NP], N - 1, np.ascontiguousarray(self.Y, dtype=np.float64), w, t0=t0,
+                               substeps=substeps, every=self.merr_nskip, stim=stim, **kw)
         path = self._pb.predict(r["x0"], r["p"], N - 1, t0=t0, substeps=substeps, stim=stim)
         res = dict(x0=r["x0"], params=r["p"], path=path, cost=r["cost"], cost_start=r["cost_start"], grad_norm=r["grad_max"],
                    nfev=r["nfev"], nit=r["nit"], status=r["status"],
